@@ -1,8 +1,13 @@
 #!/usr/bin/env python3
 """Headline benchmark: device-resident MTU-9000 TCP checksum batches (BASELINE.json).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload cfg5]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload cfg5] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nproc-per-node N --master-addr 127.0.0.1 bench.py --gpus N
+
+A plain run sets up, warms up, times the K steps, writes its outputs if
+``--dump-outputs DIR`` is given (the checksums of the last timed step, float32,
+DIR/checksums.npy) and prints the line.  ``--full`` adds the legs the headline
+figure does not need: the CPU baseline and the host end-to-end rate.
 
 With ``--gpus N > 1`` and no WORLD_SIZE in the environment, bench.py starts
 the N ranks itself (one child process per GPU, ``shard.spawn_ranks``; the
@@ -28,7 +33,8 @@ roofline: algorithmic bytes per launch (L + 2 per packet: L read, u16 written)
 cpu_baseline: pip's own pip_inet_checksum / pip_ip_checksum (oracle/_ref,
           compiled from the reference) -- or the oracle's C restatement if
           _ref is absent -- on a bounded sample of the same packets, all host
-          cores and one core; rank 0, N=1.  Beside it ("chain"): the call pip's
+          cores and one core; rank 0, N=1, under --full only (null in a plain
+          run).  Beside it ("chain"): the call pip's
           TX path makes, pip_inet{,6}_checksum_buf on a header -> payload
           pip_buf chain, over the same sample.
 roofline.traffic: PMC HBM bytes per launch from profiles/traffic_<cfg>.json,
@@ -70,7 +76,17 @@ def parse(argv=None):
     p.add_argument("--workload", default="cfg5", help="cfg1..cfg5 (default: the headline cfg5)")
     p.add_argument("--packets-per-gpu", type=int, default=0, help="override the per-GPU shard size")
     p.add_argument("--cpu-sample", type=int, default=0, help="packets in the CPU-baseline sample (0 = auto)")
-    p.add_argument("--no-cpu", action="store_true", help="skip the CPU baseline and host end-to-end legs")
+    p.add_argument("--full", action="store_true",
+                   help="after the timed steps also run what the headline figure does not need: the CPU baseline "
+                        "(pip's own code on the host cores, checked against the GPU results) and the host "
+                        "end-to-end leg; a plain run leaves cpu_baseline null")
+    p.add_argument("--no-cpu", action="store_true",
+                   help="with --full: skip the CPU baseline and host end-to-end legs (a plain run has none)")
+    p.add_argument("--dump-outputs", default="", metavar="DIR",
+                   help="after the timed steps write what the last timed step computed -- this rank's u16 checksums, "
+                        "one per packet in shard order -- as DIR/checksums.npy (float32; rank r of an N-rank run "
+                        "writes checksums_rank<r>.npy); the inputs depend on the arguments alone, so two builds "
+                        "can be compared output for output")
     p.add_argument("--results-host", action="store_true",
                    help="write the 2-B results straight into pinned host memory (where pip consumes them) instead "
                         "of HBM; the batch stays in HBM; the line says so and carries no PMC traffic figure")
@@ -160,6 +176,25 @@ def match_traffic(t: dict, kernel: str, lib_sha: str, algo_bytes: int, stride: i
     if bad:
         return None, "mismatch: " + ", ".join(bad)
     return t.get("hbm_bytes_per_launch"), "match"
+
+
+DUMP_BUDGET_BYTES = 64_000_000  # --dump-outputs: all ranks' files together stay below this
+
+
+def dump_outputs(directory: str, out, rank: int, world: int) -> Path:
+    """--dump-outputs: the u16 checksums the last timed step left in its result
+    array, as float32 (exact for u16) in packet order.  A shard too large for
+    this rank's share of the budget is sampled at a fixed even stride (packet
+    i * count // m for i < m), the same packets in every run."""
+    d = Path(directory)
+    d.mkdir(parents=True, exist_ok=True)
+    res = out.cpu().numpy().view(np.uint16)
+    m = (DUMP_BUDGET_BYTES // world - 128) // 4  # 128 B: the .npy header
+    if len(res) > m:
+        res = res[(np.arange(m, dtype=np.int64) * len(res)) // m]
+    path = d / ("checksums.npy" if world == 1 else f"checksums_rank{rank}.npy")
+    np.save(path, res.astype(np.float32))
+    return path
 
 
 def host_threads() -> int:
@@ -292,6 +327,8 @@ def run_rank(args) -> int:
         res = out.cpu().numpy().tobytes()
         digests = shard.gather_objects(env, {"rank": env.rank, "first": int(first), "count": int(count),
                                              "sha256": hashlib.sha256(res).hexdigest()})
+    if args.dump_outputs:  # what the last timed step wrote, before anything else runs
+        dump_outputs(args.dump_outputs, out, env.rank, env.world)
     total_bytes = sum(r[0] for r in ranks)
     total_pkts = sum(r[1] for r in ranks)
     one_host = len({p["host"] for p in placements}) == 1
@@ -398,7 +435,7 @@ def run_rank(args) -> int:
             line["roofline"]["rocprof_kernel_ms"] = round(rocprof_ms, 5)
             line["roofline"]["frac_rocprof"] = round(algo_bytes / (rocprof_ms / 1e3) / 1e9 / HBM_PEAK_GBS, 4)
 
-    if env.rank == 0 and env.world == 1 and not args.no_cpu:
+    if args.full and env.rank == 0 and env.world == 1 and not args.no_cpu:
         dev = (arena, lens16, tile_off) if w.ragged else None
         line["cpu_baseline"], line["host_end_to_end"] = cpu_legs(args, w, out, count, first, dev)
 

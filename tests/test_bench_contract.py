@@ -31,10 +31,12 @@ def test_traffic_attached_on_exact_match():
 
 
 @pytest.mark.parametrize("field,value", [
-    # another instantiation of the same template (ring 24 instead of 32): the r02 hole
-    ("kernel", K.replace("<false, 32, true, true>", "<false, 24, true, true>")),
-    ("kernel", K.replace("<false, 32, true, true>", "<false, 32, true, false>")),
-    ("kernel", "void pipck::k_packed"),  # a prefix is not the kernel
+    # another instantiation of the same template (ring 24 instead of 32): the r02 hole.
+    # Explicit ids: a C++ name in a test id carries "::", pytest's own separator
+    pytest.param("kernel", K.replace("<false, 32, true, true>", "<false, 24, true, true>"), id="kernel-ring24"),
+    pytest.param("kernel", K.replace("<false, 32, true, true>", "<false, 32, true, false>"),
+                 id="kernel-last-flag-false"),
+    pytest.param("kernel", "void pipck::k_packed", id="kernel-prefix"),  # a prefix is not the kernel
     ("lib_sha256", "cd" * 32),             # same name, another build
     ("lib_sha256", None),                  # a pre-r03 file without a build hash
     ("algorithmic_bytes_per_launch", 8291632672 + 16),
@@ -182,6 +184,37 @@ def test_injected_start_skew_lowers_the_aggregate(tmp_path, capfd, world):
     assert skewed["span_s"] > skewed["max_rank_s"] + 0.1
     assert skewed["rate"] < 0.75 * skewed["rate_max_rank"]
     assert skewed["rate"] == pytest.approx(world * 1e9 * 5 / skewed["span_s"])
+
+
+def test_plain_run_leaves_the_extra_legs_behind_full():
+    """The CPU baseline and host end-to-end legs run only under --full."""
+    plain = bench.parse(["--gpus", "1", "--steps", "7", "--warmup", "2"])
+    assert plain.full is False and plain.dump_outputs == "" and plain.steps == 7 and plain.warmup == 2
+    assert bench.parse(["--full"]).full is True
+    assert bench.parse(["--dump-outputs", "d"]).dump_outputs == "d"
+
+
+def test_dump_outputs_writes_the_results_within_the_budget(tmp_path, monkeypatch):
+    """--dump-outputs: the u16 results as float32 in packet order; a shard above
+    this rank's share of the byte budget is cut to an even-stride sample that is
+    the same in every run, and all ranks' files together stay within the budget."""
+    import numpy as np
+    torch = pytest.importorskip("torch")
+
+    vals = np.arange(70_001, dtype=np.uint32).astype(np.uint16)  # wraps past 65535: stored as int16 bits
+    out = torch.from_numpy(vals.view(np.int16).copy())
+    p = bench.dump_outputs(str(tmp_path / "a"), out, 0, 1)
+    got = np.load(p)
+    assert p.name == "checksums.npy" and got.dtype == np.float32
+    assert np.array_equal(got, vals.astype(np.float32)) and got.max() == 65535
+    assert bench.DUMP_BUDGET_BYTES <= 64_000_000
+    monkeypatch.setattr(bench, "DUMP_BUDGET_BYTES", 2 * (128 + 4 * 1000))
+    paths = [bench.dump_outputs(str(tmp_path / "b"), out, r, 2) for r in range(2)]
+    assert [q.name for q in paths] == ["checksums_rank0.npy", "checksums_rank1.npy"]
+    assert sum(q.stat().st_size for q in paths) <= bench.DUMP_BUDGET_BYTES
+    s = np.load(paths[0])
+    assert s.shape == (1000,) and np.array_equal(s, vals[np.arange(1000) * 70_001 // 1000].astype(np.float32))
+    assert np.array_equal(s, np.load(bench.dump_outputs(str(tmp_path / "c"), out, 0, 2)))
 
 
 def test_cpu_sample_falls_back_to_the_memory_the_host_has(monkeypatch):

@@ -270,15 +270,44 @@ def test_bench_line_names_its_kernel_and_build():
 def test_bench_results_host_line():
     """`bench.py --results-host`: the kernel writes its results into pinned host
     memory; the line says so, attaches no PMC traffic (measured with HBM
-    results), and the results still equal pip's own code on the host."""
+    results), and the results still equal pip's own code on the host (the CPU
+    baseline leg, which runs under --full)."""
     r = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--workload", "cfg2", "--steps", "2", "--warmup", "1",
-                        "--packets-per-gpu", "65536", "--results-host"], capture_output=True, text=True, timeout=300,
-                       cwd=ROOT, env=_bench_env())
+                        "--packets-per-gpu", "65536", "--results-host", "--full"], capture_output=True, text=True,
+                       timeout=300, cwd=ROOT, env=_bench_env())
     assert r.returncode == 0, r.stderr[-3000:]
     d = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][0])
     assert d["config"]["results"].startswith("pinned host memory")
     assert d["roofline"]["traffic"] is None and "--results-host" in d["roofline"]["traffic_source"]
     assert d["cpu_baseline"]["gpu_results_match"] is True
+
+
+def test_bench_plain_run_dumps_its_outputs(tmp_path, oracle):
+    """A plain run (no --full) times exactly --steps launches, leaves the CPU legs
+    out (cpu_baseline null, no host_end_to_end) and, with --dump-outputs, writes
+    the checksums its last timed step computed: float32, one per packet in
+    order, equal to pip's arithmetic on the same packets (50,001: odd, several
+    blocks)."""
+    from pip_amd.workloads import CFG2, N_FLOWS
+
+    n = 50_001
+    r = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--gpus", "1", "--workload", "cfg2", "--steps", "3",
+                        "--warmup", "1", "--packets-per-gpu", str(n), "--dump-outputs", str(tmp_path / "dump")],
+                       capture_output=True, text=True, timeout=300, cwd=ROOT, env=_bench_env())
+    assert r.returncode == 0, r.stderr[-3000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, r.stdout[-2000:]
+    d = json.loads(lines[0])
+    assert d["steps"] == 3 and d["warmup"] == 1 and d["ms_per_step"] > 0
+    assert d["ms_per_step"] == pytest.approx(d["timing"]["span_ms"] / 3, rel=1e-3)
+    assert d["cpu_baseline"] is None and "host_end_to_end" not in d
+    assert [p.name for p in (tmp_path / "dump").iterdir()] == ["checksums.npy"]
+    got = np.load(tmp_path / "dump" / "checksums.npy")
+    assert got.dtype == np.float32 and got.shape == (n,)
+    w = CFG2
+    host = oracle.gen_fixed_batch(w.seed, 0, n, w.length, w.hdr, w.stride)
+    want = oracle.batch_fixed(host, w.stride, w.length, n, 4, w.proto, w.seed, N_FLOWS, 0)
+    assert np.array_equal(got, want.astype(np.float32))
 
 
 @pytest.mark.parametrize("launcher", ["self", "torchrun"])

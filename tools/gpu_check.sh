@@ -25,7 +25,7 @@ for s in $STEPS; do
     benchall)  # every BASELINE config, each with its CPU baseline
       rc=0
       for c in ${CFGS:-1 2 3 4 5}; do
-        timeout -k 10 600 python3 bench.py --workload cfg$c --steps 20 > "$OUT/bench_cfg$c.json" \
+        timeout -k 10 600 python3 bench.py --workload cfg$c --steps 20 --full > "$OUT/bench_cfg$c.json" \
           2> "$OUT/bench_cfg$c.err" || { rc=$?; break; }
         tail -1 "$OUT/bench_cfg$c.json"
       done ;;
