@@ -443,7 +443,30 @@ uint64_t pipck_txq_inflight(const pipck_txq* q);
  * IPv6 routing header, UDP over IPv4 with a zero checksum, another protocol);
  * malformed lengths or a truncated TCP/UDP/ICMP header leave the L4 bits
  * clear; not IPv4/IPv6, 0.  IPv6 hop-by-hop / destination-options headers and
- * atomic fragments are walked to the upper layer.  Packets that lie in pinned
+ * atomic fragments are walked to the upper layer.  In full (tests/rx_reference.py
+ * restates these rules in plain integer arithmetic and every path is held to it):
+ *   - A frame under 20 bytes gets 0.  A version that is neither 4 nor 6 gets 0.
+ *   - IPv4 with IHL < 5, total length < header length, or total length > frame
+ *     length gets 0: no bit is set, PIPCK_RX_IP_OK included.  The header
+ *     checksum covers the whole header, options included (IHL 6..15).
+ *   - Version 6 with fewer than 40 bytes, or with 40 + payload length > frame
+ *     length, gets 0.
+ *   - An IPv4 fragment has MF or an offset set (ip_off & 0x3FFF != 0).  Its
+ *     verdict is IP_OK (if the header verifies) plus L4_OK.
+ *   - IPv6 walks next headers 0, 60 and 44 only.  A fragment header with an
+ *     offset or M set (field & 0xFFF9) is unchecked (3).  A routing header (43)
+ *     is unchecked (3).  A ninth extension header is unchecked (3), whatever it
+ *     holds.  An extension header that does not fit in the payload gives IP_OK
+ *     only.
+ *   - The L4 length is the IP payload length from the upper-layer offset.  The
+ *     UDP length field is not consulted.
+ *   - An L4 length under 20 (TCP) or under 8 (UDP, ICMP) leaves the L4 bits clear.
+ *   - UDP over IPv4 with a zero checksum field is unchecked (3).  UDP over IPv6
+ *     with a zero field is checked like any other value.
+ *   - Protocol 1 over IPv6 and protocol 58 over IPv4 are "another protocol" (3).
+ *   - A checksum verifies when the one's-complement sum of its range is 0xFFFF:
+ *     an all-zero ICMPv4 message (sum 0) fails.
+ * Packets that lie in pinned
  * memory (pipck_host_alloc / pipck_host_register) are read in place by the GPU
  * and their ranges held until the call returns; others are copied.  Returns
  * when every ok[i] is set; *n_verified (optional) = packets with ok == 7.

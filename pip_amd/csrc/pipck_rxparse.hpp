@@ -128,11 +128,12 @@ __device__ inline uint32_t rx_from_window(const uint8_t* p, uint32_t len, uint32
         // destination options 60 and atomic fragments 44 are walked
         uint32_t nh = win_byte(a, 6), at = 40;
         int up = 0;
-        for (int k = 0; k < 8; k++) {
+        for (int k = 0; k < 9; k++) {  // up to 8 extension headers, then the upper layer
             if (nh != 0 && nh != 60 && nh != 44) {
                 up = nh == 43 ? 0 : 1;
                 break;
             }
+            if (k == 8) break;  // a ninth extension header: unchecked (up = 0), whatever it holds
             if (at + 8 > ip_end) {
                 up = -1;
                 break;

@@ -291,12 +291,13 @@ def test_rx_verify_accepts_what_pip_emits_and_rejects_corruption():
     assert (res["ok"] == VERIFIED).all()
 
 
-def _rx_packet(oracle, rng, fam, proto, l4len, k, good=True, ext=b"", frag=0):
+def _rx_packet(oracle, rng, fam, proto, l4len, k, good=True, ext=b"", frag=0, *, options=b""):
     """An IPv4/IPv6 packet whose checksums the oracle (pip's arithmetic) filled in:
     TCP/UDP over their pseudo-headers, ICMPv4 over the message alone
     (pip_ip_checksum), ICMPv6 over the IPv6 pseudo-header (next header 58).
     ext: IPv6 extension headers before the upper layer, as _ext() returns them;
-    frag: IPv4 ip_off."""
+    frag: IPv4 ip_off; options: IPv4 option bytes (a multiple of 4, at most 40)
+    after the fixed header, covered by the header checksum."""
     import struct
 
     l4 = bytearray(rng.randbytes(l4len))
@@ -317,8 +318,9 @@ def _rx_packet(oracle, rng, fam, proto, l4len, k, good=True, ext=b"", frag=0):
                 c = 0xFFFF  # never "no checksum" by accident (either verifies: both mean zero)
             l4[field:field + 2] = struct.pack(">H", c)
     if fam == 4:
-        hdr = bytearray(struct.pack(">BBHHHBBH4s4s", 0x45, 0, 20 + l4len, k & 0xFFFF, frag or 0x4000, 64, proto, 0,
-                                    src, dst))
+        assert len(options) % 4 == 0 and len(options) <= 40
+        hdr = bytearray(struct.pack(">BBHHHBBH4s4s", 0x40 | (5 + len(options) // 4), 0, 20 + len(options) + l4len,
+                                    k & 0xFFFF, frag or 0x4000, 64, proto, 0, src, dst) + bytes(options))
         hdr[10:12] = struct.pack(">H", oracle.ip_checksum(bytes(hdr)))
     else:
         chain, first = ext if ext else (b"", proto)
@@ -346,39 +348,48 @@ def _ext(chain, upper):
     return out, types[0]
 
 
-@pytest.mark.gpu
-def test_rx_verify_against_the_oracle(oracle):
-    """Random TCP/UDP over IPv4 and IPv6 packets whose checksums the oracle
-    (pip's arithmetic) filled in -- odd lengths, options, UDP over IPv4 without
-    a checksum, ICMP -- all verify; the same packets with a wrong L4 checksum
-    fail bit 1 only."""
+def _oracle_packets(oracle):
+    """The packets of test_rx_verify_against_the_oracle: (good, checked, broken)
+    -- 3,000 oracle-checksummed packets (one IPv4 packet in four with 4-40 bytes
+    of options, drawn from a generator of their own), whether each one's payload
+    is checked, and the same packets with a wrong L4 checksum."""
     import random
-    import struct
-
-    import numpy as np
 
     rng = random.Random(11)
+    orng = random.Random(1111)
     good, checked = [], []
     for k in range(3000):
         fam = rng.choice([4, 6])
         proto = rng.choice([6, 17, 17, 1]) if fam == 4 else rng.choice([6, 17, 58])
         l4len = rng.randint(20 if proto == 6 else 8, 3000)
-        p = _rx_packet(oracle, rng, fam, proto, l4len, k)
+        options = orng.randbytes(4 * orng.randint(1, 10)) if fam == 4 and orng.randrange(4) == 0 else b""
+        p = _rx_packet(oracle, rng, fam, proto, l4len, k, options=options)
         good.append(p + rng.randbytes(rng.choice([0, 0, 6])))  # trailing link padding
         checked.append(not (fam == 4 and proto == 17 and k % 7 == 0))
-    ok = _verify(good)
-    for o, c in zip(ok, checked):
-        assert o == (VERIFIED if c else UNCHECKED), o
     broken = []
     for p in good:
         v4 = p[0] >> 4 == 4
-        hl = 20 if v4 else 40
+        hl = (p[0] & 15) * 4 if v4 else 40
         proto = p[9] if v4 else p[6]
         field = {6: 16, 17: 6, 1: 2, 58: 2}[proto]
         q = bytearray(p)
         if not (v4 and proto == 17 and q[hl + 6] == 0 and q[hl + 7] == 0):
             q[hl + field] ^= 0x01
         broken.append(bytes(q))
+    return good, checked, broken
+
+
+@pytest.mark.gpu
+def test_rx_verify_against_the_oracle(oracle):
+    """Random TCP/UDP over IPv4 and IPv6 packets whose checksums the oracle
+    (pip's arithmetic) filled in -- odd lengths, options, UDP over IPv4 without
+    a checksum, ICMP -- all verify; the same packets with a wrong L4 checksum
+    fail bit 1 only."""
+    good, checked, broken = _oracle_packets(oracle)
+    assert sum(p[0] > 0x45 and p[0] >> 4 == 4 for p in good) > 200  # IPv4 options are present
+    ok = _verify(good)
+    for o, c in zip(ok, checked):
+        assert o == (VERIFIED if c else UNCHECKED), o
     ok = _verify(broken)
     for c, o in zip(checked, ok):
         # a damaged TCP / UDP / ICMPv4 / ICMPv6 checksum: checked, and only its bit fails
@@ -393,6 +404,25 @@ def test_rx_verify_fragments_extension_headers_and_other_protocols(oracle):
     and routing headers, protocols without a known checksum.  IPv6 hop-by-hop /
     destination-options headers and atomic fragments are walked to the upper
     layer and checked."""
+    cases, walked, bad, overlong, short = _unchecked_and_walked_cases(oracle)
+    ok = _verify([c for c, _ in cases])
+    for (p, want), o in zip(cases, ok):
+        assert o == want, (p[:48].hex(), o, want)
+    # the walked ones really are checked: damage the upper layer's checksum field
+    assert (_verify(bad) == IP_OK | L4_CHECKED).all()
+    # an extension header whose length runs past the payload: malformed, no L4 bits
+    assert list(_verify([overlong])) == [IP_OK]
+    # truncated ICMP (under 8 bytes) and TCP headers: no L4 bits
+    assert list(_verify(short)) == [IP_OK, IP_OK, IP_OK]
+
+
+def _unchecked_and_walked_cases(oracle):
+    """The labelled packets of
+    test_rx_verify_fragments_extension_headers_and_other_protocols: (cases,
+    walked, bad, overlong, short) -- (packet, verdict) pairs; the pairs'
+    walked-and-verified packets, and those with the upper layer's checksum
+    field damaged (IP_OK | L4_CHECKED); a packet whose extension header runs
+    past the payload (IP_OK); and three truncated L4 headers (IP_OK each)."""
     import random
 
     rng = random.Random(5)
@@ -415,10 +445,6 @@ def test_rx_verify_fragments_extension_headers_and_other_protocols(oracle):
         cases.append((_rx_packet(oracle, rng, 4, 47, 40, k), UNCHECKED))
         cases.append((_rx_packet(oracle, rng, 6, 50, 40, k), UNCHECKED))
         cases.append((_rx_packet(oracle, rng, 6, 1, 40, k), UNCHECKED))
-    ok = _verify([c for c, _ in cases])
-    for (p, want), o in zip(cases, ok):
-        assert o == want, (p[:48].hex(), o, want)
-    # the walked ones really are checked: damage the upper layer's checksum field
     walked = [p for p, w in cases if w == VERIFIED]
     bad = []
     for p in walked:
@@ -428,14 +454,10 @@ def test_rx_verify_fragments_extension_headers_and_other_protocols(oracle):
             nh, at = q[at], at + (8 if nh == 44 else 8 * (q[at + 1] + 1))
         q[at + {6: 16, 17: 6, 58: 2}[nh]] ^= 0x40
         bad.append(bytes(q))
-    assert (_verify(bad) == IP_OK | L4_CHECKED).all()
-    # an extension header whose length runs past the payload: malformed, no L4 bits
     p = bytearray(_rx_packet(oracle, rng, 6, 6, 40, 1, ext=_ext([(0, 0)], 6)))
     p[41] = 30  # hop-by-hop Hdr Ext Len: 248 bytes, past the 48-byte payload
-    assert list(_verify([bytes(p)])) == [IP_OK]
-    # truncated ICMP (under 8 bytes) and TCP headers: no L4 bits
     short = [_rx_packet(oracle, rng, 4, 1, 4, 1), _rx_packet(oracle, rng, 6, 58, 6, 1), _rx_packet(oracle, rng, 4, 6, 12, 1)]
-    assert list(_verify(short)) == [IP_OK, IP_OK, IP_OK]
+    return cases, walked, bad, bytes(p), short
 
 
 @pytest.mark.gpu

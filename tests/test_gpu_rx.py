@@ -33,15 +33,12 @@ def _run(lib, q, ptrs, lens):
     return ok[:n]
 
 
-@pytest.mark.gpu
-def test_rx_verify_c_abi_chunks_jumbo_and_staging(oracle):
-    """More packets than one kernel launch takes (2,048), lengths up to 64 KB
-    (many rows per wave), heap packets that grow the staging copy in the middle
-    of a call, pinned packets at odd addresses read in place, and damage in the
-    header, the payload or the checksum field -- each caught in its own bit."""
-    from pip_amd import _lib
-
-    rng = random.Random(101)
+def _labelled_packets(oracle, seed, paddings):
+    """5,000 oracle-checksummed IPv4/IPv6 TCP/UDP/ICMP packets up to 64 KB, each
+    with the verdict its construction gives it: every fourth damaged in an L4
+    byte, every fourth IPv4 one in a header byte only the header checksum
+    covers, link padding of one of `paddings` bytes after the IP length."""
+    rng = random.Random(seed)
     pkts, want = [], []
     for k in range(5000):
         fam = rng.choice([4, 6])
@@ -62,8 +59,20 @@ def test_rx_verify_c_abi_chunks_jumbo_and_staging(oracle):
         elif r == 2 and fam == 4:
             p[rng.choice([1, 4, 5, 8, 10, 11])] ^= 0x40  # an IPv4 header byte only its own checksum covers
             w &= ~IP_OK
-        pkts.append(bytes(p) + rng.randbytes(rng.choice([0, 3])))  # link padding after the IP length
+        pkts.append(bytes(p) + rng.randbytes(rng.choice(paddings)))  # link padding after the IP length
         want.append(w)
+    return pkts, want
+
+
+@pytest.mark.gpu
+def test_rx_verify_c_abi_chunks_jumbo_and_staging(oracle):
+    """More packets than one kernel launch takes (2,048), lengths up to 64 KB
+    (many rows per wave), heap packets that grow the staging copy in the middle
+    of a call, pinned packets at odd addresses read in place, and damage in the
+    header, the payload or the checksum field -- each caught in its own bit."""
+    from pip_amd import _lib
+
+    pkts, want = _labelled_packets(oracle, 101, [0, 3])
     lib, q = _rxq()
     try:
         heap = [C.create_string_buffer(p, len(p)) for p in pkts]
@@ -175,28 +184,7 @@ def test_rx_verify_device_equals_host_path(oracle, tile_waves):
 
     from pip_amd import engine
 
-    rng = random.Random(202)
-    pkts, want = [], []
-    for k in range(5000):
-        fam = rng.choice([4, 6])
-        proto = rng.choice([6, 17, 1]) if fam == 4 else rng.choice([6, 17, 58])
-        l4len = rng.choice([rng.randint(20, 1500), rng.randint(8000, 9000), rng.randint(60000, 65400)]) \
-            if k % 50 == 0 else rng.randint(20, 1500)
-        p = bytearray(_rx_packet(oracle, rng, fam, proto, l4len, k + 1))
-        checked = not (fam == 4 and proto == 17 and (k + 1) % 7 == 0)
-        w = VERIFIED if checked else UNCHECKED
-        hl = 20 if fam == 4 else 40
-        if k % 4 == 1 and checked:
-            i = rng.randrange(hl, len(p))
-            if fam == 4 and proto == 17 and i in (hl + 6, hl + 7):
-                i = hl
-            p[i] ^= 0x08
-            w = IP_OK | L4_CHECKED
-        elif k % 4 == 2 and fam == 4:
-            p[rng.choice([1, 4, 5, 8, 10, 11])] ^= 0x40
-            w &= ~IP_OK
-        pkts.append(bytes(p) + rng.randbytes(rng.choice([0, 3, 17])))
-        want.append(w)
+    pkts, want = _labelled_packets(oracle, 202, [0, 3, 17])
     arena, lens, tile_off = _device_batch(pkts)
     ok = engine.rx_verify_device(arena, lens, tile_off).cpu().numpy()
     assert _rx_kernel_waves() == tile_waves
@@ -217,24 +205,7 @@ def test_rx_verify_device_edges(oracle, tile_waves):
     path's (pipck_rx_verify on the same bytes)."""
     from pip_amd import engine
 
-    rng = random.Random(5)
-    zero_icmp = _ipv4(oracle, 1, bytes(8))                        # T = 0: checksum should be 0xFFFF
-    ffff_icmp = _ipv4(oracle, 1, bytes(8) + b"\xff\xff")          # T = 0xFFFF: checksum 0, verifies
-    cases = [
-        (b"", 0), (bytes(19), 0), (bytes([0x45]) + bytes(30), 0), (bytes([0x55]) + bytes(60), 0),
-        (_rx_packet(oracle, rng, 6, 6, 200, 1, ext=_ext([(0, 0), (60, 1)], 6)), VERIFIED),
-        (_rx_packet(oracle, rng, 6, 17, 300, 2, ext=_ext([(0, 20), (60, 3)], 17)), VERIFIED),  # past 80 B
-        (_rx_packet(oracle, rng, 6, 58, 64, 3, ext=_ext([(44, 0)], 58)), VERIFIED),   # atomic fragment
-        (_rx_packet(oracle, rng, 6, 17, 200, 4, ext=_ext([(44, 0x0001)], 17)), UNCHECKED),
-        (_rx_packet(oracle, rng, 6, 6, 200, 5, ext=_ext([(43, 0)], 6)), UNCHECKED),   # routing header
-        (_rx_packet(oracle, rng, 4, 6, 40, 6, frag=0x2000), UNCHECKED),
-        (_rx_packet(oracle, rng, 4, 17, 100, 7), UNCHECKED),                          # k % 7 == 0: no UDP sum
-        (_rx_packet(oracle, rng, 4, 1, 8, 8), VERIFIED),
-        (_rx_packet(oracle, rng, 4, 6, 40, 9)[:20 + 12], None),                       # truncated TCP
-        (_rx_packet(oracle, rng, 4, 6, 20, 10) + bytes(100), VERIFIED),               # long link padding
-        (_rx_packet(oracle, rng, 6, 6, 20, 11) + rng.randbytes(90), VERIFIED),
-        (zero_icmp, IP_OK | L4_CHECKED), (ffff_icmp, VERIFIED),
-    ]
+    cases = _device_edge_cases(oracle)
     frames = [p for p, _ in cases]
     lib, q = _rxq()
     try:
@@ -255,6 +226,29 @@ def test_rx_verify_device_edges(oracle, tile_waves):
     dev2 = engine.rx_verify_device(arena, lens, tile_off).cpu().numpy()
     assert _rx_kernel_waves() == tile_waves
     assert list(dev2) == [host[i] for i in keep]
+
+
+def _device_edge_cases(oracle):
+    """The case table of test_rx_verify_device_edges: (frame, verdict), None
+    where the table leaves the verdict to the host path."""
+    rng = random.Random(5)
+    zero_icmp = _ipv4(oracle, 1, bytes(8))                        # T = 0: checksum should be 0xFFFF
+    ffff_icmp = _ipv4(oracle, 1, bytes(8) + b"\xff\xff")          # T = 0xFFFF: checksum 0, verifies
+    return [
+        (b"", 0), (bytes(19), 0), (bytes([0x45]) + bytes(30), 0), (bytes([0x55]) + bytes(60), 0),
+        (_rx_packet(oracle, rng, 6, 6, 200, 1, ext=_ext([(0, 0), (60, 1)], 6)), VERIFIED),
+        (_rx_packet(oracle, rng, 6, 17, 300, 2, ext=_ext([(0, 20), (60, 3)], 17)), VERIFIED),  # past 80 B
+        (_rx_packet(oracle, rng, 6, 58, 64, 3, ext=_ext([(44, 0)], 58)), VERIFIED),   # atomic fragment
+        (_rx_packet(oracle, rng, 6, 17, 200, 4, ext=_ext([(44, 0x0001)], 17)), UNCHECKED),
+        (_rx_packet(oracle, rng, 6, 6, 200, 5, ext=_ext([(43, 0)], 6)), UNCHECKED),   # routing header
+        (_rx_packet(oracle, rng, 4, 6, 40, 6, frag=0x2000), UNCHECKED),
+        (_rx_packet(oracle, rng, 4, 17, 100, 7), UNCHECKED),                          # k % 7 == 0: no UDP sum
+        (_rx_packet(oracle, rng, 4, 1, 8, 8), VERIFIED),
+        (_rx_packet(oracle, rng, 4, 6, 40, 9)[:20 + 12], None),                       # truncated TCP
+        (_rx_packet(oracle, rng, 4, 6, 20, 10) + bytes(100), VERIFIED),               # long link padding
+        (_rx_packet(oracle, rng, 6, 6, 20, 11) + rng.randbytes(90), VERIFIED),
+        (zero_icmp, IP_OK | L4_CHECKED), (ffff_icmp, VERIFIED),
+    ]
 
 
 @pytest.mark.gpu

@@ -169,3 +169,115 @@ def test_update_corner_cases_pseudo(oracle):
         exp[i, ck_off], exp[i, ck_off + 1] = c >> 8, c & 0xFF
     bad = np.nonzero((got != exp).any(axis=1))[0]
     assert bad.size == 0, f"{bad.size} mismatches, first rows {bad[:5]}"
+
+
+# ---- the update inside a frame: covers that start at a real L3 / L4 offset -------
+
+# cover_off, cover_len, family, proto, ck_off, edit_off, edit_len, stride, new_stride, flows
+FRAME_CASES = {
+    "tcp4_odd_cover": (20, 61, 4, 6, 36, 20, 4, 96, 8, "implicit"),
+    "tcp4_long_edit": (34, 1480, 4, 6, 50, 54, 1200, 1520, 1216, "implicit"),
+    "udp6_nat_odd_edit_ends_cover": (54, 33, 6, 17, 60, 86, 1, 96, 8, "nat"),
+    "ip_odd_cover_off": (1, 20, 0, 0, 11, 13, 8, 23, 8, "none"),
+    "ip_no_edit": (14, 20, 0, 0, 24, 0, 0, 40, 0, "none"),
+    "udp6_explicit_flows": (40, 8, 6, 17, 46, 40, 4, 64, 8, "explicit"),
+    "tcp4_flow_origin": (20, 20, 4, 6, 36, 24, 8, 48, 8, "origin"),
+}
+FRAME_N_FLOWS = 7
+_frame_cache = {}
+
+
+def _frame_case(oracle, name, n):
+    """Host side of one case, computed once: the arena before (every packet
+    carrying pip's checksum of its cover under the old flow), the edit bytes,
+    the flow tables, and the arena expected after -- edit applied, field zeroed,
+    pip's checksum of the cover under the new flow stored big-endian; every
+    other byte as before."""
+    if (name, n) in _frame_cache:
+        return _frame_cache[name, n]
+    cover_off, cover_len, family, proto, ck_off, edit_off, edit_len, stride, new_stride, flows = FRAME_CASES[name]
+    rng = np.random.default_rng(sorted(FRAME_CASES).index(name) * 1000 + n)
+    pk = rng.integers(0, 256, (n, stride), dtype=np.uint8)
+    new = rng.integers(0, 256, (n, max(new_stride, 1)), dtype=np.uint8)
+    q = (n + 3) // 4  # a quarter of the packets: covers and edits of 0x00 / 0xFF bytes, the 0x0000 / 0xFFFF corner
+    pk[:q, cover_off:cover_off + cover_len] = _corner_batch(rng, q, cover_len)
+    new[:q] = np.where(rng.random((q, new.shape[1])) < 0.3, 0xFF, 0)
+    alen = {0: 0, 4: 4, 6: 16}[family]
+
+    def table():
+        return [(bytes(rng.integers(0, 256, alen, dtype=np.uint8)), bytes(rng.integers(0, 256, alen, dtype=np.uint8)))
+                for _ in range(FRAME_N_FLOWS)]
+
+    old_tab = table() if family else None
+    new_tab = table() if flows == "nat" else old_tab
+    origin = {"origin": 4093, "explicit": 99}.get(flows, 0)
+    flow_of = rng.integers(0, FRAME_N_FLOWS, n).astype(np.int32) if flows == "explicit" else None
+    flow = flow_of if flow_of is not None else (origin + np.arange(n)) % FRAME_N_FLOWS
+
+    def pip(row, tab, i):
+        cover = row[cover_off:cover_off + cover_len].tobytes()
+        if not family:
+            return oracle.ip_checksum(cover)
+        s, d = tab[int(flow[i])]
+        return (oracle.inet_checksum if family == 4 else oracle.inet6_checksum)(cover, proto, s, d)
+
+    def fill(rows, tab):
+        rows[:, ck_off:ck_off + 2] = 0
+        for i in range(n):
+            c = pip(rows[i], tab, i)
+            rows[i, ck_off], rows[i, ck_off + 1] = c >> 8, c & 0xFF
+
+    fill(pk, old_tab)
+    exp = pk.copy()
+    exp[:, edit_off:edit_off + edit_len] = new[:, :edit_len]
+    fill(exp, new_tab)
+    rec = (lambda t: b"".join(s + d + bytes([proto, 0, 0, 0]) for s, d in t))
+    case = dict(pk=pk, new=new, exp=exp, flow_of=flow_of, origin=origin,
+                old=rec(old_tab) if family else None, new_flows=rec(new_tab) if family else None)
+    _frame_cache[name, n] = case
+    return case
+
+
+@pytest.mark.parametrize("misalign", [0, 13])
+@pytest.mark.parametrize("name,n", [(k, 2000) for k in FRAME_CASES] + [("tcp4_odd_cover", k) for k in (1, 255, 256, 257)])
+def test_update_inside_a_frame(oracle, name, n, misalign):
+    """pipck_update_fixed where the header says it is used: the cover is an L4
+    segment (or an IPv4 header) that starts 1, 14, 20, 34, 40 or 54 bytes into
+    each frame, with odd covers, an edit of 1,200 bytes, an odd edit ending the
+    cover, no edit at all, NAT to a second flow table, explicit flow indices and
+    a flow origin, in an arena that starts 0 or 13 bytes past a 16-byte boundary
+    and in batches around the 256-thread block.  The kernel rewrites frames in
+    place, so the WHOLE arena -- the bytes before and after every cover, the
+    stride padding, the guard bytes around the arena -- must equal the frames
+    with the edit applied and pip's recomputed checksum (oracle.ip_checksum /
+    inet_checksum / inet6_checksum of the cover under the new flow) stored
+    big-endian; verify_fixed over the covers then accepts every packet."""
+    from tests.test_gpu_parity import upload
+
+    cover_off, cover_len, family, proto, ck_off, edit_off, edit_len, stride, new_stride, flows = FRAME_CASES[name]
+    c = _frame_case(oracle, name, n)
+    if not family and n == 2000:  # both stored corner values occur among the expected fields
+        ck = _field(c["exp"].reshape(-1), stride, n, ck_off)
+        assert (ck == 0).any() and (ck == 0xFFFF).any()
+    whole, arena = upload(c["pk"].reshape(-1), misalign)
+    p_old = p_new = None
+    if family:
+        p_old = engine.prepare_flows(family, engine.flows_to_device(family, c["old"]), FRAME_N_FLOWS)
+        p_new = engine.prepare_flows(family, engine.flows_to_device(family, c["new_flows"]), FRAME_N_FLOWS)
+    flow_of = torch.from_numpy(c["flow_of"]).to(DEV) if c["flow_of"] is not None else None
+    new_d = torch.from_numpy(c["new"]).to(DEV).view(-1) if edit_len else None
+    err = torch.zeros(1, dtype=torch.int32, device=DEV)
+    engine.update_fixed(arena, stride, n, cover_off, cover_len, ck_off, edit_off, edit_len, new_d, new_stride,
+                        p_old, p_new, FRAME_N_FLOWS if family else None, flow_of, c["origin"], err)
+    assert int(err.item()) == 0
+    got = whole.cpu().numpy()
+    assert not got[:misalign].any() and not got[misalign + n * stride:].any()  # nothing written around the arena
+    rows = got[misalign:misalign + n * stride].reshape(n, stride)
+    bad = np.nonzero((rows != c["exp"]).any(axis=1))[0]
+    assert bad.size == 0, (f"{bad.size} of {n} frames differ, first {bad[:3]}: byte offsets "
+                           f"{np.nonzero(rows[bad[0]] != c['exp'][bad[0]])[0][:8]} got "
+                           f"{rows[bad[0]][max(ck_off - 2, 0):ck_off + 4].tobytes().hex()} want "
+                           f"{c['exp'][bad[0]][max(ck_off - 2, 0):ck_off + 4].tobytes().hex()}")
+    ok = engine.verify_fixed(arena[cover_off:], stride, cover_len, n, p_new, FRAME_N_FLOWS if family else None,
+                             flow_of, c["origin"])
+    assert bool((ok == 1).all())

@@ -299,7 +299,10 @@ def test_bench_plain_run_dumps_its_outputs(tmp_path, oracle):
     assert len(lines) == 1, r.stdout[-2000:]
     d = json.loads(lines[0])
     assert d["steps"] == 3 and d["warmup"] == 1 and d["ms_per_step"] > 0
-    assert d["ms_per_step"] == pytest.approx(d["timing"]["span_ms"] / 3, rel=1e-3)
+    # the same elapsed time twice (bench.py: ms_per_step = span / steps), each printed with 4
+    # decimals of a millisecond: the two roundings alone separate them by up to 0.5e-4 +
+    # 0.5e-4 / 3 ms, more than 1e-3 of a ~0.03 ms step, so that much is always allowed
+    assert d["ms_per_step"] == pytest.approx(d["timing"]["span_ms"] / 3, rel=1e-3, abs=0.5e-4 * (1 + 1 / 3) + 1e-9)
     assert d["cpu_baseline"] is None and "host_end_to_end" not in d
     assert [p.name for p in (tmp_path / "dump").iterdir()] == ["checksums.npy"]
     got = np.load(tmp_path / "dump" / "checksums.npy")
