@@ -54,9 +54,9 @@ const char* pipck_last_error(void);
  * checked) -- 1.0's single "ok == 3" meant verified.  1.2: the bounded _n forms
  * of the ragged, chain and ring calls.  1.3: the bounded _n forms of the
  * fixed-stride calls (pipck_checksum_fixed_n, pipck_verify_fixed_n,
- * pipck_update_fixed_n). */
+ * pipck_update_fixed_n).  1.4: pipck_tx_fill_device. */
 #define PIPCK_VERSION_MAJOR 1
-#define PIPCK_VERSION_MINOR 3
+#define PIPCK_VERSION_MINOR 4
 uint32_t pipck_version(void);
 
 /* ---- flows / pseudo-headers ------------------------------------------ */
@@ -526,6 +526,76 @@ int pipck_rx_verify_ring(const void* d_arena, uint64_t slot_stride, const uint16
  * *n_verified (optional) = frames with ok == PIPCK_RX_VERIFIED. */
 int pipck_host_rx_verify_packed(pipck_ctx* ctx, const void* h_frames, const uint16_t* h_lens, uint64_t n_frames,
                                 uint8_t* h_ok, uint64_t* n_verified);
+
+/* ---- TX checksum fill of frames already in DEVICE memory ------------------
+ * The TX mirror of pipck_rx_verify_device.  pip checksums every segment it
+ * sends and stores htons(result) into the header: th_sum
+ * (pip/protocol/pip_tcp_packet.cpp:124-134), uh_sum (pip/protocol/pip_udp.cpp:
+ * 40-61), ip_sum (pip/pip_netif.cpp:80-97).  pipck_tx_fill_device does that for
+ * n whole IP frames in the byte-packed layout of pipck_checksum_packed_bytes
+ * (frame i of d_lens[i] bytes at d_arena + b_i, d_tile_off from
+ * pipck_packed_bytes_index; link padding after the IP length allowed): it
+ * parses each frame as pipck_rx_verify_device does, computes the IPv4 header
+ * checksum and the TCP / UDP / ICMP / ICMPv6 checksum, and stores both fields
+ * IN PLACE -- exactly the bytes pip's TX path writes.  d_done[i] receives
+ *   PIPCK_TX_IP_FILLED   the IPv4 header checksum field (bytes 10-11) was written
+ *   PIPCK_TX_L4_FILLED   the TCP / UDP / ICMP / ICMPv6 checksum field was written
+ * A field is "taken as zero": its current bytes are ignored, so filling a frame
+ * twice gives the same bytes.  No byte outside those two fields is ever written.
+ * In full (tests/tx_reference.py restates these rules in plain integer
+ * arithmetic and the kernel is held to it byte for byte):
+ *   - Frames that are not written (d_done 0, no byte stored): a frame under 20
+ *     bytes; a version that is neither 4 nor 6; IPv4 with IHL < 5, total length
+ *     < header length, or total length > frame length; version 6 with fewer
+ *     than 40 bytes, or with 40 + payload length > frame length.
+ *   - IPv4 header: bytes 10-11 receive, big-endian, pip_ip_checksum
+ *     (pip_checksum.cpp:35-39) of the whole header, options included (IHL
+ *     5..15), with the field taken as zero; PIPCK_TX_IP_FILLED is set.  IPv6
+ *     has no header checksum, so the bit stays clear.
+ *   - An IPv4 fragment has MF or an offset set (ip_off & 0x3FFF != 0).  It gets
+ *     the header field only.
+ *   - The upper layer is located exactly as on RX.  IPv6 walks next headers 0,
+ *     60 and 44 only, at most 8 of them.  Nothing more is written when a
+ *     fragment header carries an offset or M (field & 0xFFF9), when a routing
+ *     header (43) appears, when there is a ninth extension header, whatever it
+ *     holds, or when an extension header does not fit in the payload.
+ *   - The L4 length is the IP payload length from the upper-layer offset.  The
+ *     UDP length field is not consulted.
+ *   - The protocols are TCP (6), UDP (17), ICMP (1) over IPv4 only and ICMPv6
+ *     (58) over IPv6 only.  Any other protocol (protocol 1 over IPv6 and 58
+ *     over IPv4 included) gets nothing more.
+ *   - An L4 length under 20 (TCP) or under 8 (UDP, ICMP, ICMPv6) gets nothing more.
+ *   - The L4 field sits at message offset 16 (TCP), 6 (UDP) or 2 (ICMP,
+ *     ICMPv6).  It receives, big-endian, pip_inet_checksum (IPv4) or
+ *     pip_inet6_checksum (IPv6) of the message with the field taken as zero,
+ *     over the frame's own addresses, protocol and L4 length
+ *     (pip_checksum.cpp:42-87); ICMP over IPv4 has no pseudo-header and gets
+ *     pip_ip_checksum of the message.  PIPCK_TX_L4_FILLED is set.
+ *   - UDP over IPv4 is filled whatever the field held: there is no "zero means
+ *     no checksum" rule on TX.
+ *   - pip's values are stored as they are: a computed 0x0000 is stored as
+ *     0x0000 (see the top of this header).  With PIPCK_TX_UDP_ZERO_AS_ONES in
+ *     flags, a computed zero for UDP, over IPv4 or IPv6, is stored as 0xFFFF
+ *     (RFC 768; RFC 8200 section 8.1).  An all-zero ICMP-over-IPv4 message
+ *     (its field apart) gets pip's ~fold(0) = 0xFFFF.
+ *   - Link padding after the IP length is not summed and not written.
+ * Layout, alignment and index exactly as pipck_rx_verify_device: the arena
+ * 128-byte aligned and readable to the 16-byte boundary after the last frame.
+ * Bounded the same way: a tile of 64 frames whose bytes, as d_tile_off and
+ * d_lens place them, reach past arena_bytes is neither read nor written, its
+ * frames get d_done 0 and d_err (optional, device u32) gets
+ * (1 << PIPCK_ERANGE).  PIPCK_EINVAL for a null pointer, an arena that is not
+ * 128-byte aligned or unknown bits in flags; n_packets == 0 returns PIPCK_OK.
+ * One kernel on `stream`, asynchronous, with no host-side allocation and no
+ * host work (capturable in a graph): the byte-packed stream sums every frame
+ * once, then a lane per frame parses its headers, derives both checksums from
+ * that one sum and stores them.  The frames of one call must not be read or
+ * written by other work on the device while it runs. */
+#define PIPCK_TX_IP_FILLED 1u
+#define PIPCK_TX_L4_FILLED 2u
+#define PIPCK_TX_UDP_ZERO_AS_ONES 1u /* flags bit 0 */
+int pipck_tx_fill_device(void* d_arena, uint64_t arena_bytes, const uint16_t* d_lens, const uint64_t* d_tile_off,
+                         uint64_t n_packets, uint32_t flags, uint8_t* d_done, uint32_t* d_err, void* stream);
 
 #ifdef __cplusplus
 }

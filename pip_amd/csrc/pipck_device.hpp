@@ -155,6 +155,18 @@ __device__ __forceinline__ void store_result8(buf_t r, uint32_t byte_off, uint32
     __builtin_amdgcn_raw_buffer_store_b8((uint8_t)v, r, (int)byte_off, 0, kStoreSc1);
 }
 
+// In-place checksum-field stores of k_packedb_tx (pipck_tx_fill_device): one byte
+// each, range-checked like the loads, with the default cache policy.  The two
+// to four bytes of a frame mostly share one 128-B line, and a plain store lets
+// the L2 merge them into one write; with the write-through policy of the
+// result stores above each byte is a fabric write of its own (64-B frames: the
+// call takes 1.95x the RX verifier's time against 1.46x; 1,500-B frames 1.51x
+// against 1.48x, 9,000-B frames 1.22x against 1.20x; non-temporal stores are
+// slower than either everywhere but at 64 B, profiles/r07_tx_fill_device.jsonl).
+__device__ __forceinline__ void store_field8(buf_t r, uint32_t byte_off, uint32_t v) {
+    __builtin_amdgcn_raw_buffer_store_b8((uint8_t)v, r, (int)byte_off, 0, 0);
+}
+
 // ---- wave-level helpers (wave64) shared by the streaming kernels
 __device__ __forceinline__ void wave_sync() {
     __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");

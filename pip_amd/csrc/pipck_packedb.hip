@@ -31,8 +31,19 @@
 #include "pipck_common.hpp"
 #include "pipck_device.hpp"
 #include "pipck_rxparse.hpp"
+#include "pipck_txparse.hpp"
 
 namespace pipck {
+
+// What the tile's end does with each packet's sum.  The stream helpers take the
+// mode too (they only ask whether header windows are captured): each kernel
+// family then has instantiations of its own, and adding one leaves the code the
+// compiler makes for the others exactly as it was.
+enum PackedbMode : int {
+    kPbSum = 0,  // k_packedb: the checksum, or its verdict, with the flow's pseudo-header
+    kPbRx = 1,   // k_packedb_rx: the frame's headers parsed and judged (PIPCK_RX_* bits)
+    kPbTx = 2,   // k_packedb_tx: the frame's headers parsed and its checksum fields stored in place
+};
 
 // W = the waves that stream one tile together (rows dealt round-robin)
 template <int W>
@@ -61,7 +72,7 @@ __device__ __forceinline__ void packedb_flush(PackedbLdsT<W>& t, int lane, uint3
 // nv valid packets.  S0 / e0: the slot holding the row's first byte and its
 // end byte (scalars, carried across rows).
 //
-// RX (k_packedb_rx): the row also hands every packet the chunks of its header
+// RX and TX (MODE kPbRx, kPbTx): the row also hands every packet the chunks of its header
 // window -- the six aligned chunks from the one holding its first byte, as far
 // as the packet reaches -- into hdr[k * 64 + packet] in LDS, so the tile's end
 // parses headers without reading them from memory again.  A chunk whose first
@@ -69,7 +80,7 @@ __device__ __forceinline__ void packedb_flush(PackedbLdsT<W>& t, int lane, uint3
 // k < 6; a chunk holding a packet boundary is window chunk 0 of the packet
 // that starts inside it.  (Tiles with a packet under 16 bytes take the
 // lane-per-segment path and read their headers from memory.)
-template <bool RX, int W>
+template <int MODE, int W>
 __device__ __forceinline__ void packedb_reduce_row(PackedbLdsT<W>& t, uint32_t w, u32x4* hdr, uint32_t row,
                                                    uint32_t total, int lane,
                                                    const u32x4& v, uint32_t start_v, uint32_t end_v,
@@ -89,7 +100,7 @@ __device__ __forceinline__ void packedb_reduce_row(PackedbLdsT<W>& t, uint32_t w
             rslot = S0;
         }
         racc = dot4(v, racc);
-        if (RX && S0 >= 1 && S0 <= nv) {  // the row may hold the last chunks of packet S0 - 1's window
+        if (MODE != kPbSum && S0 >= 1 && S0 <= nv) {  // the row may hold the last chunks of packet S0 - 1's window
             const uint32_t cs = (uint32_t)__builtin_amdgcn_readfirstlane((int)(t.end[S0 - 1] >> 4));
             if (row < cs + 6u) {  // wave-uniform
                 const uint32_t k = row + (uint32_t)lane - cs;
@@ -130,7 +141,7 @@ __device__ __forceinline__ void packedb_reduce_row(PackedbLdsT<W>& t, uint32_t w
     const uint32_t add = (tail ? inc + (S == S0 ? R : 0u) : 0u) - (hd ? inc - lo : 0u);
     if (tail || hd) atomicAdd(&t.acc[S], add);
     if (active && p < 16) atomicAdd(&t.acc[S + 1], val - lo);
-    if (RX && active) {
+    if (MODE != kPbSum && active) {
         if (S >= 1 && S <= nv) {  // the chunk's first byte is in packet S - 1
             const uint32_t k = c - (t.end[S - 1] >> 4);
             if (k < 6u) hdr[k * 64u + S - 1] = v;
@@ -143,7 +154,7 @@ __device__ __forceinline__ void packedb_reduce_row(PackedbLdsT<W>& t, uint32_t w
 
 // The tile's 1 KiB rows w, w + W, w + 2W, ... (W = 1: every row), a ring of
 // U rows in flight.
-template <int U, bool NT, bool RX, int W>
+template <int U, bool NT, int MODE, int W>
 __device__ __forceinline__ void packedb_stream(PackedbLdsT<W>& t, uint32_t w, u32x4* hdr, uint32_t total, int lane,
                                                uintptr_t base, uint32_t start_v, uint32_t end_v, uint32_t mfirst_v,
                                                bool valid, uint32_t nv) {
@@ -163,7 +174,7 @@ __device__ __forceinline__ void packedb_stream(PackedbLdsT<W>& t, uint32_t w, u3
         for (int u = 0; u < U; u++) {
             const uint32_t row = c0 + u * 64 * W;
             if (row < total)  // wave-uniform
-                packedb_reduce_row<RX, W>(t, w, hdr, row, total, lane, v[u], start_v, end_v, mfirst_v, valid, nv, S0,
+                packedb_reduce_row<MODE, W>(t, w, hdr, row, total, lane, v[u], start_v, end_v, mfirst_v, valid, nv, S0,
                                           e0, racc, rslot);
             // unconditional reload (past the tile: zeros, no request), so each
             // reduce waits for its own row only (vmcnt(U-1))
@@ -190,11 +201,29 @@ __device__ __forceinline__ uint32_t packedb_lane_sum(uintptr_t base, uint32_t st
     return acc;
 }
 
-// The kernel body.  RX = true (k_packedb_rx: pipck_rx_verify_device,
+// The kernel body.  MODE kPbRx (k_packedb_rx: pipck_rx_verify_device,
 // pipck_rxdev.hip): each frame's sum feeds rx_device_one (pipck_rxparse.hpp) at
 // the tile's end and the ok byte carries the PIPCK_RX_* bits (VERIFY true, no
-// pseudo-header).
-template <bool VERIFY, int U, bool NT, bool RX, int W>
+// pseudo-header).  MODE kPbTx (k_packedb_tx: pipck_tx_fill_device): the same
+// stream and header windows; each frame's sum feeds tx_from_window
+// (pipck_txparse.hpp), the frame's own lane stores its IPv4 header and L4
+// checksum fields into the arena, and the ok byte carries the PIPCK_TX_* bits
+// (VERIFY true, no pseudo-header; n_flows carries the call's flags).
+//
+// kPbTx's stores.  Only wave 0 stores, and only after the block-wide barrier that
+// ends the tile's stream (or, for a tile holding a frame under 16 bytes, after
+// its own lane-path reads): every byte this block reads of its own frames is in
+// registers or LDS by then, and each lane computes both of its values before it
+// stores either.  A neighbouring tile's block may load, at any time, the 16-byte
+// chunks or the 128-byte line that hold these bytes -- its stream starts at the
+// line holding its first byte and ends at the chunk holding its last -- but the
+// bytes of another tile's frames fall into a slot that block discards (slot 0,
+// or the slot past its last packet) and never enter its header windows, so no
+// result depends on whether such a load sees the old or the new bytes.  No byte
+// outside a frame's own two fields is ever stored: each field goes out as two
+// single-byte stores (it may sit at any parity and straddle a 16-byte chunk or a
+// 128-byte line), range-checked against the tile's own bytes.
+template <bool VERIFY, int U, bool NT, int MODE, int W>
 __device__ __forceinline__ void packedb_body(PackedbLdsT<W>& t, u32x4* hdr, const uint8_t* __restrict__ arena,
                                              const uint16_t* __restrict__ lens, const uint64_t* __restrict__ tile_off,
                                              uint64_t n, const uint32_t* __restrict__ pseudo, uint32_t n_flows,
@@ -260,7 +289,7 @@ __device__ __forceinline__ void packedb_body(PackedbLdsT<W>& t, u32x4* hdr, cons
     } else {
         const uint32_t mfirst = (start + 15u) >> 4;  // first chunk whose first byte is in this packet
         const uint32_t total = (end_last + 15u) >> 4;
-        packedb_stream<U, NT, RX, W>(t, w, hdr, total, lane, base, start, end, mfirst, valid, nv);
+        packedb_stream<U, NT, MODE, W>(t, w, hdr, total, lane, base, start, end, mfirst, valid, nv);
         if (W > 1) {
             __syncthreads();  // every wave's rows are in the slot partials
             if (w != 0) return;  // wave 0 finishes the tile
@@ -273,7 +302,7 @@ __device__ __forceinline__ void packedb_body(PackedbLdsT<W>& t, u32x4* hdr, cons
     const uint32_t F = (start & 1u) ? f16 : bswap16(f16);  // byte order from the packet's start parity
     const uint32_t P = pseudo ? Pbase + len : 0u;
     uint32_t r;
-    if (RX) {  // the frame's header window: captured from the stream, or (lane path) read again
+    if (MODE != kPbSum) {  // the frame's header window: captured from the stream, or (lane path) read again
         const uint8_t* pk = reinterpret_cast<const uint8_t*>(base + start);
         uint32_t hw[24];
         if (lane_path) {
@@ -285,7 +314,22 @@ __device__ __forceinline__ void packedb_body(PackedbLdsT<W>& t, u32x4* hdr, cons
                 hw[4 * k] = x.x, hw[4 * k + 1] = x.y, hw[4 * k + 2] = x.z, hw[4 * k + 3] = x.w;
             }
         }
-        r = valid ? rx_from_window(pk, len, F, hw) : 0u;
+        if (MODE == kPbTx) {
+            const TxFill fill = valid ? tx_from_window(pk, len, F, hw, n_flows) : TxFill{0u, 0u, 0u, 0u};
+            // both values are known: store them, through a resource that ends with the tile's last frame
+            const buf_t wb = buf_rsrc(reinterpret_cast<const void*>(base), end_last);
+            if (fill.done & kTxIp) {
+                store_field8(wb, start + 10u, fill.ip_val >> 8);
+                store_field8(wb, start + 11u, fill.ip_val & 0xFFu);
+            }
+            if (fill.done & kTxL4) {
+                store_field8(wb, start + fill.l4_at, fill.l4_val >> 8);
+                store_field8(wb, start + fill.l4_at + 1u, fill.l4_val & 0xFFu);
+            }
+            r = fill.done;
+        } else {
+            r = valid ? rx_from_window(pk, len, F, hw) : 0u;
+        }
     } else {
         r = VERIFY ? (uint32_t)(fold16(P + F) == 0xFFFFu) : (uint32_t)finish(P, F);
         if (fbad) {
@@ -315,7 +359,7 @@ __global__ __launch_bounds__(64 * W) void k_packedb(const uint8_t* __restrict__ 
                                                     uint16_t* __restrict__ out, uint8_t* __restrict__ ok,
                                                     uint64_t arena_bytes, uint32_t* __restrict__ err) {
     __shared__ PackedbLdsT<W> t;
-    packedb_body<VERIFY, U, NT, false, W>(t, nullptr, arena, lens, tile_off, n, pseudo, n_flows, flow_of,
+    packedb_body<VERIFY, U, NT, kPbSum, W>(t, nullptr, arena, lens, tile_off, n, pseudo, n_flows, flow_of,
                                           flow_origin, out, ok, arena_bytes, err);
 }
 
@@ -328,8 +372,21 @@ __global__ __launch_bounds__(64 * W) void k_packedb_rx(const uint8_t* __restrict
                                                        uint32_t* __restrict__ err) {
     __shared__ PackedbLdsT<W> t;
     __shared__ u32x4 hdr[6 * 64];  // header windows: chunk k of packet s at hdr[k * 64 + s]
-    packedb_body<true, U, NT, true, W>(t, hdr, arena, lens, tile_off, n, nullptr, 1u, nullptr, 0, nullptr, ok,
-                                       arena_bytes, err);
+    packedb_body<true, U, NT, kPbRx, W>(t, hdr, arena, lens, tile_off, n, nullptr, 1u, nullptr, 0, nullptr, ok,
+                                        arena_bytes, err);
+}
+
+// frames to be sent: the stream, then each tile's headers parsed and both
+// checksum fields of every frame stored in place (see packedb_body)
+template <int U, bool NT, int W>
+__global__ __launch_bounds__(64 * W) void k_packedb_tx(uint8_t* arena, const uint16_t* __restrict__ lens,
+                                                       const uint64_t* __restrict__ tile_off, uint64_t n,
+                                                       uint32_t flags, uint8_t* __restrict__ done,
+                                                       uint64_t arena_bytes, uint32_t* __restrict__ err) {
+    __shared__ PackedbLdsT<W> t;
+    __shared__ u32x4 hdr[6 * 64];  // header windows, as k_packedb_rx
+    packedb_body<true, U, NT, kPbTx, W>(t, hdr, arena, lens, tile_off, n, nullptr, flags, nullptr, 0, nullptr, done,
+                                        arena_bytes, err);
 }
 
 // The (W, U) a launch uses, as W * 100 + U.  Internal tune loads_per_lane 32 =
@@ -468,6 +525,46 @@ int launch_packedb_rx(const void* d_arena, uint64_t arena_bytes, const uint16_t*
     return PIPCK_OK;
 }
 
+// pipck_tx_fill_device: the byte-packed stream with both checksum fields of
+// every frame stored at each tile's end (argument checks, launch shapes and the
+// tune switch as launch_packedb_rx, plus the flags)
+int launch_packedb_tx(void* d_arena, uint64_t arena_bytes, const uint16_t* d_lens, const uint64_t* d_tile_off,
+                      uint64_t n, uint32_t flags, uint8_t* d_done, uint32_t* d_err, hipStream_t s) {
+    if (flags & ~(uint32_t)PIPCK_TX_UDP_ZERO_AS_ONES) {
+        set_error("pipck_tx_fill_device: unknown flag bits");
+        return PIPCK_EINVAL;
+    }
+    if (n == 0) return PIPCK_OK;
+    if (!d_arena || !d_lens || !d_tile_off || !d_done) {
+        set_error("pipck_tx_fill_device: null pointer");
+        return PIPCK_EINVAL;
+    }
+    if ((uintptr_t)d_arena % 128) {
+        set_error("pipck_tx_fill_device: the arena must be 128-byte aligned");
+        return PIPCK_EINVAL;
+    }
+    const uint64_t tiles = (n + 63) / 64;
+    if (tiles > 0x7FFFFFFFull) {
+        set_error("pipck_tx_fill_device: more than 2^37 packets in one launch");
+        return PIPCK_ERANGE;
+    }
+    uint8_t* a = (uint8_t*)d_arena;
+#define PIPCK_PBTX(WW, UU)                                                                                     \
+    case WW * 100 + UU:                                                                                        \
+        PIPCK_LAUNCH((k_packedb_tx<UU, true, WW>), dim3((uint32_t)tiles), dim3(64 * WW), 0, s, a, d_lens,       \
+                     d_tile_off, n, flags, d_done, arena_bytes, d_err);                                        \
+        break
+    switch (packedb_shape(true)) {
+        PIPCK_PBTX(1, 32);
+        PIPCK_PBTX(2, 16);
+        default:
+        PIPCK_PBTX(4, 8);
+    }
+#undef PIPCK_PBTX
+    PIPCK_LAUNCHED("k_packedb_tx");
+    return PIPCK_OK;
+}
+
 }  // namespace pipck
 
 using namespace pipck;
@@ -503,6 +600,11 @@ int pipck_verify_packed_bytes(const void* d_arena, const uint16_t* d_lens, const
                               uint64_t flow_origin, uint8_t* d_ok, void* stream) {
     return launch_packedb(true, d_arena, UINT64_MAX, d_lens, d_tile_off, n, d_pseudo, n_flows, d_flow_of,
                           flow_origin, nullptr, d_ok, nullptr, as_stream(stream), false);
+}
+
+int pipck_tx_fill_device(void* d_arena, uint64_t arena_bytes, const uint16_t* d_lens, const uint64_t* d_tile_off,
+                         uint64_t n, uint32_t flags, uint8_t* d_done, uint32_t* d_err, void* stream) {
+    return launch_packedb_tx(d_arena, arena_bytes, d_lens, d_tile_off, n, flags, d_done, d_err, as_stream(stream));
 }
 
 int pipck_packed_bytes_index(const uint16_t* d_lens, uint64_t n, uint64_t* d_tile_off, void* stream) {

@@ -358,6 +358,26 @@ def rx_verify_device(arena, lens, tile_off, n: int | None = None, ok=None, err=N
     return ok
 
 
+TX_IP_FILLED, TX_L4_FILLED = 1, 2  # PIPCK_TX_* bits of tx_fill_device's done bytes
+TX_UDP_ZERO_AS_ONES = 1  # flags bit 0
+
+
+def tx_fill_device(arena, lens, tile_off, n: int | None = None, flags: int = 0, done=None, err=None):
+    """IP frames about to be sent, in device memory, byte-packed (pipck_tx_fill_device): the IPv4
+    header checksum and the TCP / UDP / ICMP / ICMPv6 checksum of every frame are computed and
+    stored into `arena` in place, as pip's TX path writes them; returns the PIPCK_TX_* bits per
+    frame (uint8).  flags: TX_UDP_ZERO_AS_ONES.  Tiles are bounded by the arena's size on the
+    device: one reaching past it is neither read nor written (err as checksum_packed)."""
+    torch = _torch()
+    n = lens.numel() if n is None else n
+    if done is None:
+        done = torch.empty(n, dtype=torch.uint8, device=arena.device)
+    _check_packed(arena, lens, tile_off, n, unit=1)
+    call("pipck_tx_fill_device", _ptr(arena), _nbytes(arena), _ptr(lens), _ptr(tile_off), n, flags, _ptr(done),
+         _ptr(err), current_stream(arena.device))
+    return done
+
+
 def packed_bytes_index(lens, n: int | None = None):
     """tile_off for a byte-packed batch: the byte offset of every 64th packet (u64 as int64) + the total."""
     torch = _torch()

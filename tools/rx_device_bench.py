@@ -13,6 +13,16 @@ the whole verifier (k_packedb<RX>: the same stream with each tile's headers
 parsed and judged at its end), as frame bytes per second vs the 8 TB/s HBM
 peak; algorithmic bytes = frame bytes read + the 2-B sum / 1-B verdict
 written per packet.
+
+    python tools/rx_device_bench.py --tx-mixes 64,1500,9000,0
+
+times pipck_tx_fill_device (k_packedb_tx) against pipck_rx_verify_device
+(k_packedb_rx) on the same arenas in one process: per mix (an L4 length for every
+frame, 0 = the Zipf mix) the legs RX, TX, RX again rotate over the rounds, so the
+two RX medians give the run-to-run spread the TX / RX ratio is read against.  The
+frames already carry pip's checksums, so the TX leg must leave the arena byte for
+byte as it was (checked), whatever it costs to store them again.  One JSON line
+per mix, with the library's sha256.
 """
 from __future__ import annotations
 
@@ -46,6 +56,65 @@ def traffic_ratio(tag: str, kernel: str, algo_bytes: int) -> dict:
     return {"traffic": tb, "traffic_ratio": round(tb / algo_bytes, 4)}
 
 
+def tx_vs_rx(a):
+    """The --tx-mixes legs (see the module docstring)."""
+    import hashlib
+
+    import numpy as np
+    import torch
+
+    from bench import last_kernel
+    from pip_amd import engine
+    from size_scan import timed_b2b
+
+    engine.require_gpu()
+    from pip_amd import _lib
+
+    sha = hashlib.sha256(_lib.LIBPIPCK.read_bytes()).hexdigest()  # the build this process loaded
+    for l4 in [int(x) for x in a.tx_mixes.split(",")]:
+        n = a.packets if l4 == 0 else min(a.packets, (8 << 30) // (l4 + 30))  # at most ~8 GiB of frames
+        arena, lens, tile_off, _, _, _ = engine.gen_rx_frames(n, 11, l4_len=l4)
+        total, nbytes = int(tile_off[-1].item()), arena.numel()
+        ok = torch.empty(n, dtype=torch.uint8, device="cuda")
+        done = torch.empty(n, dtype=torch.uint8, device="cuda")
+        before = arena.clone()
+
+        def rx():
+            engine.call("pipck_rx_verify_device", engine._ptr(arena), nbytes, engine._ptr(lens), engine._ptr(tile_off),
+                        n, engine._ptr(ok), None, engine.current_stream())
+
+        def tx():
+            engine.call("pipck_tx_fill_device", engine._ptr(arena), nbytes, engine._ptr(lens), engine._ptr(tile_off),
+                        n, 0, engine._ptr(done), None, engine.current_stream())
+
+        legs = [("rx_a", rx), ("tx", tx), ("rx_b", rx)]
+        ms = {k: [] for k, _ in legs}
+        kern = {}
+        for rnd in range(a.rounds):
+            for name, fn in legs[rnd % 3:] + legs[:rnd % 3]:
+                for _ in range(a.warm):
+                    fn()
+                ms[name].append(timed_b2b(fn, a.iters))
+                kern[name] = last_kernel().split("(")[0]
+        unchanged = bool(torch.equal(arena, before))
+        med = {k: statistics.median(v) for k, v in ms.items()}
+        rx_mean = (med["rx_a"] + med["rx_b"]) / 2
+        hist = lambda t: {int(k): int(c) for k, c in zip(*np.unique(t.cpu().numpy(), return_counts=True))}  # noqa: E731
+        print(json.dumps({"what": "tx_fill_device_vs_rx_verify_device", "l4_len": l4 or "zipf", "packets": n,
+                          "frame_bytes": total, "rx_kernel": kern["rx_a"], "tx_kernel": kern["tx"],
+                          **{k + "_ms": round(v, 4) for k, v in med.items()},
+                          **{k + "_rounds_ms": [round(x, 4) for x in v] for k, v in ms.items()},
+                          "tx_over_rx": round(med["tx"] / rx_mean, 4),
+                          "rx_spread": round(abs(med["rx_a"] - med["rx_b"]) / rx_mean, 4),
+                          "tx_GBps": round((total + n) / med["tx"] / 1e6, 1),
+                          "tx_frac": round((total + n) / med["tx"] / 1e6 / 8000, 4),
+                          "arena_unchanged_by_tx": unchanged, "done": hist(done), "verdicts": hist(ok),
+                          "lib_sha256": sha}), flush=True)
+        assert unchanged, "pipck_tx_fill_device changed frames that already carried pip's checksums"
+        del arena, before, lens, tile_off, ok, done
+        torch.cuda.empty_cache()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--packets", type=int, default=8 << 20)
@@ -58,7 +127,11 @@ def main():
     ap.add_argument("--arms", default="groups,kring,rows,slots",
                     help="ring schedules to time; groups:NAME = the default with --tunes[NAME]")
     ap.add_argument("--tunes", default="{}", help='JSON {"NAME": engine.tune kwargs} for groups:NAME arms')
+    ap.add_argument("--tx-mixes", default="",
+                    help="L4 lengths (0 = Zipf) for the TX-against-RX legs; nothing else runs")
     a = ap.parse_args()
+    if a.tx_mixes:
+        return tx_vs_rx(a)
     tune_default = json.loads(a.tune)
     tunes = json.loads(a.tunes)
     import torch
