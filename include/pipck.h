@@ -317,7 +317,12 @@ typedef struct pipck_hseg {
  *   sum = init; for each seg: sum = fold(fold((sum + sum16be(seg)) mod 2^32))
  * (pip_standard_checksum, pip_checksum.cpp:13-33, chained as at :110-112).
  * *out receives the final folded u32 in [0, 0xFFFF].  nseg == 0 behaves as one
- * empty segment (a pip_buf chain is never empty).  Synchronous. */
+ * empty segment (a pip_buf chain is never empty).  A segment with len == 0 may
+ * have a null ptr and counts as empty; init is any u32 (the accumulator wraps
+ * mod 2^32 with the data exactly as pip's does).  The 68 KiB of
+ * pipck_ctx_zero_copy's modes 2-4 counts staged bytes, not payload bytes:
+ * need = roundup16(16 * nseg) + sum of roundup16(len), a 16-byte table entry
+ * per segment and every segment padded to 16 bytes.  Synchronous. */
 int pipck_host_sum(pipck_ctx* ctx, const pipck_hseg* segs, uint32_t nseg, uint32_t init, uint32_t* out);
 
 /* Host-resident fixed-stride batch: H2D in chunks, kernel, D2H of results,
