@@ -9,6 +9,7 @@
 
 #include "../../include/pipck.h"
 #include "pipck_testing.h"
+#include "pipck_tune.hpp"
 
 namespace pipck {
 
@@ -81,17 +82,20 @@ int chains_unchecked(const void* d_arena, const pipck_desc* d_segs, uint64_t n_s
                      uint16_t* d_out, uint32_t* d_err, hipStream_t s, uint64_t arena_bytes = UINT64_MAX,
                      uint32_t n_flows = UINT32_MAX);
 
+// The launch functions below take the caller's snapshot of the tuning state
+// (pipck_tune.hpp): rows, ring, load policy and the kernels' flag word come from it.
+
 // The block-cooperative flat stream (pipck_coop.hip); PIPCK_EINVAL when the
 // shape does not fit its block tasks (the caller then takes k_flat).
 int launch_flat_coop(bool verify, const void* d_arena, uint64_t stride, uint32_t len, uint64_t n,
                      const uint32_t* d_pseudo, uint32_t n_flows, const uint32_t* d_flow_of, uint64_t flow_origin,
-                     uint16_t* d_out, uint8_t* d_ok, uint32_t* d_err, hipStream_t s, uint32_t rows_per_wave,
-                     uint32_t ring, uint32_t kflags);
+                     uint16_t* d_out, uint8_t* d_ok, uint32_t* d_err, hipStream_t s, const TuneView& tv);
 
 // The header row stream (pipck_hdr.hip): 20/24-byte strides, no pseudo-header;
-// PIPCK_EINVAL when the shape does not fit (the caller then takes k_small).
+// PIPCK_EINVAL when the shape or the batch size does not fit (the caller then
+// takes k_small).
 int launch_hdr(bool verify, const void* d_arena, uint64_t stride, uint32_t len, uint64_t n, uint16_t* d_out,
-               uint8_t* d_ok, hipStream_t s, uint32_t rows, uint32_t ring, bool nt, uint32_t kflags, bool coop = false);
+               uint8_t* d_ok, hipStream_t s, const TuneView& tv);
 
 // pipck_rx_verify_device (pipck_packedb.hip): k_packedb with the RX verdicts.
 int launch_ring_rx(const void* d_arena, uint64_t stride, const uint16_t* d_lens, uint64_t n, uint8_t* d_ok,
@@ -99,20 +103,11 @@ int launch_ring_rx(const void* d_arena, uint64_t stride, const uint16_t* d_lens,
 int launch_packedb_rx(const void* d_arena, uint64_t arena_bytes, const uint16_t* d_lens, const uint64_t* d_tile_off,
                       uint64_t n, uint8_t* d_ok, uint32_t* d_err, hipStream_t s);
 
-// The one-packet-per-wave measurement arm (pipck_wave.hip; pipck_tune
-// lanes_per_packet == kWaveArm): fixed strides (desc == false) or descriptors.
-constexpr uint32_t kWaveArm = 256;
-bool wave_arm();  // pipck_tune(kWaveArm, ...) is in force (pipck_kernels.hip)
-bool alt_schedule();  // pipck_tune flag bit 28 (the other schedule) is set
-uint32_t g_tune_flags();  // pipck_tune's flags / loads_per_lane in force
-uint32_t g_tune_loads();
-uint32_t g_tune_blocks();
-// measurement-only probes that change results (pipck_tune_probes, pipck_testing.h)
-constexpr uint32_t kProbeHdrInPlace = 1u;
-extern std::atomic<uint32_t> g_probes;
+// The one-packet-per-wave measurement arm (pipck_wave.hip; TuneView::wave_arm()):
+// fixed strides (desc == false) or descriptors.
 int launch_wave(bool verify, bool desc, const void* d_arena, uint64_t stride, uint32_t len, const pipck_desc* d_desc,
                 uint64_t n, const uint32_t* d_pseudo, uint32_t n_flows, const uint32_t* d_flow_of,
                 uint64_t flow_origin, uint16_t* d_out, uint8_t* d_ok, uint32_t* d_err, hipStream_t s,
-                uint32_t max_chunks, uint32_t nl, uint64_t arena_bytes = UINT64_MAX);
+                uint32_t max_chunks, const TuneView& tv, uint64_t arena_bytes = UINT64_MAX);
 
 }  // namespace pipck

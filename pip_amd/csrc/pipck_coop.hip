@@ -29,11 +29,6 @@
 
 namespace pipck {
 
-// pipck_tune flags bits 21 / 22 (MEASUREMENT ONLY, no results), as for k_flat:
-// consume every row with one add and skip the per-row work / skip the task end
-constexpr uint32_t kCoopLoadsOnly = 1u << 21;
-constexpr uint32_t kCoopNoEnd = 1u << 22;
-
 template <int U>
 constexpr int coop_waves_per_simd() { return U >= 32 ? 2 : (U >= 24 ? 3 : (U >= 16 ? 4 : 5)); }
 
@@ -47,7 +42,7 @@ __device__ __forceinline__ void coop_body(uint32_t* s_part, const uint8_t* __res
                                           uint32_t n_flows, const uint32_t* __restrict__ flow_of, uint64_t flow_origin,
                                           uint16_t* __restrict__ out, uint8_t* __restrict__ ok, uint32_t kflags,
                                           uint32_t* __restrict__ err) {
-    if (!PROBE) kflags &= ~(kCoopLoadsOnly | kCoopNoEnd);
+    if (!PROBE) kflags &= ~(kLoadsOnly | kNoTaskEnd);
     const int lane = threadIdx.x & 63;
     const uint32_t w = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     const uint32_t pitch = coop_pitch(K);
@@ -84,7 +79,7 @@ __device__ __forceinline__ void coop_body(uint32_t* s_part, const uint8_t* __res
 #pragma unroll
         for (int u = 0; u < U; u++) {
             const uint32_t j = j0 + u;
-            if (j < my_rows && (kflags & kCoopLoadsOnly)) {  // measurement: consume the row, no per-row work
+            if (j < my_rows && (kflags & kLoadsOnly)) {  // measurement: consume the row, no per-row work
                 probe += v[u].x;
             } else if (j < my_rows) {  // wave-uniform
                 // lane's chunk: k0 + lane chunks into packet pkt (at most one boundary: cpp >= 64)
@@ -111,7 +106,7 @@ __device__ __forceinline__ void coop_body(uint32_t* s_part, const uint8_t* __res
         }
     }
     __syncthreads();
-    if (kflags & (kCoopLoadsOnly | kCoopNoEnd)) {  // measurement only: no results
+    if (kflags & (kLoadsOnly | kNoTaskEnd)) {  // measurement only: no results
         if (probe == 0x9E3779B9u) s_part[0] = probe;
         return;
     }
@@ -158,18 +153,18 @@ typedef void (*coop_fn)(const uint8_t*, uint32_t, uint32_t, uint64_t, uint32_t, 
 // Launch for an aligned arena, 16-B-multiple stride in [1 KiB, 64 KiB], len <=
 // stride (checked by the caller); n_flows as launch_fixed hands it to every
 // fixed kernel (the modulus, or with d_flow_of the entries' bound).
-// rows_per_wave: task size target (0 = auto);
-// ring: rows in flight per wave (0 = auto).  Returns PIPCK_OK, or PIPCK_EINVAL
-// when the shape does not fit a block task (the caller then uses k_flat).
+// tv.rows(): task size target in rows per wave (0 = auto); tv.loads: rows in
+// flight per wave, by thresholds (0 = auto, >= 32 / >= 24 / else = ring 32 /
+// 24 / 16).  Returns PIPCK_OK, or PIPCK_EINVAL when the shape does not fit a
+// block task (the caller then uses k_flat).
 int launch_flat_coop(bool verify, const void* d_arena, uint64_t stride, uint32_t len, uint64_t n,
                      const uint32_t* d_pseudo, uint32_t n_flows, const uint32_t* d_flow_of, uint64_t flow_origin,
-                     uint16_t* d_out, uint8_t* d_ok, uint32_t* d_err, hipStream_t s, uint32_t rows_per_wave,
-                     uint32_t ring, uint32_t kflags) {
+                     uint16_t* d_out, uint8_t* d_ok, uint32_t* d_err, hipStream_t s, const TuneView& tv) {
     const uint32_t cpp = (uint32_t)(stride / 16);
     const bool jumbo = cpp >= 256;
     // rows per wave: 64 for jumbo packets (cfg5: 24 packets per block task;
     // 48 rows lost 7 %, 80 rows 0.4 %), 48 for shorter ones (cfg2: 128 packets)
-    const uint32_t rpw = rows_per_wave ? rows_per_wave : (jumbo ? 64u : 48u);
+    const uint32_t rpw = tv.rows() ? tv.rows() : (jumbo ? 64u : 48u);
     // K packets per block task: ~4 * rpw rows, a multiple of 8 packets (8 * stride
     // is a multiple of 128 B), at most 256 (one packet per thread at the end)
     uint32_t K = (4u * rpw * 64u) / cpp;
@@ -181,7 +176,7 @@ int launch_flat_coop(bool verify, const void* d_arena, uint64_t stride, uint32_t
     const uint32_t nf = n_flows ? n_flows : 1u;
     // a ring of 32 rows at every stride (2 waves/SIMD): at 1,488-B strides
     // 0.887-0.891 ms against 0.894-0.897 for 24 (profiles/r04_cfg2_coop_scan.jsonl)
-    const uint32_t u = ring ? ring : 32u;
+    const uint32_t u = tv.loads ? tv.loads : 32u;
     static const coop_fn kCoop[3][2] = {  // [ring 16 / 24 / 32][verify], non-temporal loads
         {k_flat_coop<16, false, true>, k_flat_coop<16, true, true>},
         {k_flat_coop<24, false, true>, k_flat_coop<24, true, true>},
@@ -189,9 +184,10 @@ int launch_flat_coop(bool verify, const void* d_arena, uint64_t stride, uint32_t
     static const coop_fn kCoopProbe[3] = {k_flat_coop_probe<16, false, true>, k_flat_coop_probe<24, false, true>,
                                           k_flat_coop_probe<32, false, true>};
     const int ui = u >= 32 ? 2 : (u >= 24 ? 1 : 0);
-    const bool probe = (kflags & (kCoopLoadsOnly | kCoopNoEnd)) && !verify;
-    PIPCK_LAUNCH(probe ? kCoopProbe[ui] : kCoop[ui][verify], dim3((uint32_t)blocks), dim3(256), lds, s, (const uint8_t*)d_arena, cpp, len, n,
-                 K, d_pseudo, nf, d_flow_of, flow_origin, d_out, d_ok, kflags, d_err);
+    const bool probe = (tv.flags & (kLoadsOnly | kNoTaskEnd)) && !verify;
+    PIPCK_LAUNCH(probe ? kCoopProbe[ui] : kCoop[ui][verify], dim3((uint32_t)blocks), dim3(256), lds, s,
+                 (const uint8_t*)d_arena, cpp, len, n, K, d_pseudo, nf, d_flow_of, flow_origin, d_out, d_ok, tv.flags,
+                 d_err);
     PIPCK_LAUNCHED("k_flat_coop");
     return PIPCK_OK;
 }

@@ -32,19 +32,8 @@
 
 namespace pipck {
 
-// tune flags (same results): bit 29 = k_hdr's result stores plain write-back,
-// bit 30 = non-temporal (default: write-through, sc1); bit 31 = one store per
-// result instead of 16-byte pieces
-constexpr uint32_t kHdrPlainStores = 1u << 29;
-constexpr uint32_t kHdrNtStores = 1u << 30;
-constexpr uint32_t kHdrNarrowStores = 1u << 31;
-// measurement only (pipck_tune_probes, not a tune flag --
-// the flags' settings all compute the same results): store each header's checksum
-// INTO the header -- htons(result) at byte 10, its ip_sum, as pip_netif.cpp:97
-// stores it -- instead of into the result array (which is left untouched): the
-// "results inside the headers" layout, to weigh its write-back of whole dirty
-// lines against the separate 2-byte result stream.
-constexpr uint32_t kHdrInPlace = 1u << 28;  // the kernel's own flag word only (launch_hdr sets it)
+// (k_hdr's flag word -- kHdrInPlace and the kHdr*Stores policy -- is in pipck_tune.hpp)
+constexpr uint64_t kHdrMinBatch = 8ull << 20;  // headers: k_hdr from here, k_small below
 
 template <int D>
 struct HdrGeom {
@@ -192,12 +181,20 @@ __global__ __launch_bounds__(256) void k_hdr(const uint8_t* __restrict__ arena, 
 typedef void (*hdr_fn)(const uint8_t*, uint32_t, uint64_t, uint32_t, uint16_t*, uint8_t*, uint32_t);
 
 // Launch for a 16-byte-aligned arena, stride 20 or 24, len <= stride, no
-// pseudo-header.  rows: 1 KiB-ish rows per wave task (0 = auto); ring: rows in
-// flight per wave (8 / 16 / 24 / 32, 0 = auto).  PIPCK_EINVAL when the shape does
-// not fit (the caller then takes k_small).
+// pseudo-header.  tv.rows(): 1 KiB-ish rows per wave task (0 = auto).
+// tv.loads 8/16/24/32 = one task per wave with that ring, 9/17/25/33 = the
+// block-cooperative row order with ring 8/16/24/32, either at any batch size;
+// 1 = never k_hdr; anything else = a ring of 32 from kHdrMinBatch headers up.
+// PIPCK_EINVAL when the shape or the size does not fit (the caller then takes
+// k_small).
 int launch_hdr(bool verify, const void* d_arena, uint64_t stride, uint32_t len, uint64_t n, uint16_t* d_out,
-               uint8_t* d_ok, hipStream_t s, uint32_t rows, uint32_t ring, bool nt, uint32_t kflags, bool coop) {
+               uint8_t* d_ok, hipStream_t s, const TuneView& tv) {
+    const uint32_t lq = tv.loads;
+    const bool force = lq == 8 || lq == 16 || lq == 24 || lq == 32;
+    const bool coop = lq == 9 || lq == 17 || lq == 25 || lq == 33;
+    if (lq == 1 || !(force || coop || n >= kHdrMinBatch)) return PIPCK_EINVAL;
     if ((stride != 20 && stride != 24) || len > stride || (uintptr_t)d_arena % 16) return PIPCK_EINVAL;
+    const uint32_t rows = tv.rows();
     const uint32_t PR = stride == 20 ? HdrGeom<5>::PR : HdrGeom<6>::PR;
     // rows per wave task: 32 with a ring of 32 (the whole task in flight at
     // once) measured fastest at 128M-256M headers -- 0.979 ms at 256M vs
@@ -210,10 +207,10 @@ int launch_hdr(bool verify, const void* d_arena, uint64_t stride, uint32_t len, 
     const uint64_t blocks = (tasks + 3) / 4;
     if (blocks > 0x7FFFFFFFull || per * stride >= (1ull << 31)) return PIPCK_EINVAL;
     const size_t lds = 4u * per * sizeof(uint16_t);
-    const uint32_t u = ring ? ring : 32u;
+    const uint32_t u = force ? lq : (coop ? lq - 1 : 32u);
     // bit 28 of the tune flags is the other fixed-stride schedule elsewhere (same
     // results); here it carries the in-place probe only when that probe is on
-    kflags = (kflags & ~kHdrInPlace) | ((g_probes.load() & kProbeHdrInPlace) ? kHdrInPlace : 0u);
+    const uint32_t kflags = (tv.flags & ~kHdrInPlace) | ((tv.probes & kProbeHdrInPlace) ? kHdrInPlace : 0u);
     const int ui = u >= 32 ? 3 : (u >= 24 ? 2 : (u >= 16 ? 1 : 0));
 #define PIPCK_HD(D, U, CO) {{k_hdr<D, U, false, false, CO>, k_hdr<D, U, false, true, CO>}, \
                            {k_hdr<D, U, true, false, CO>, k_hdr<D, U, true, true, CO>}}
@@ -224,7 +221,7 @@ int launch_hdr(bool verify, const void* d_arena, uint64_t stride, uint32_t len, 
          {PIPCK_HD(6, 8, true), PIPCK_HD(6, 16, true), PIPCK_HD(6, 24, true), PIPCK_HD(6, 32, true)}}};
 #undef PIPCK_HD
     // a block covers 4 x R rows either way: four wave tasks, or one cooperative task
-    PIPCK_LAUNCH(kHdr[coop][stride == 24][ui][verify][nt], dim3((uint32_t)blocks), dim3(256), lds, s,
+    PIPCK_LAUNCH(kHdr[coop][stride == 24][ui][verify][tv.nt(true)], dim3((uint32_t)blocks), dim3(256), lds, s,
                  (const uint8_t*)d_arena, len, n, R, d_out, d_ok, kflags);
     PIPCK_LAUNCHED("k_hdr");
     return PIPCK_OK;

@@ -72,11 +72,6 @@ __global__ void k_flows6(const pipck_flow6* __restrict__ f, uint32_t n, uint32_t
     pseudo[i] = s + f[i].proto;
 }
 
-// tune flags bit 29 (same results): k_flat / k_packed store their results
-// with plain write-back stores (the r02 policy) instead of the write-through
-// sc1 stores (store_result16)
-constexpr uint32_t kPlainResultStores = 1u << 29;
-
 // ---------------------------------------------------------------------------
 // fixed-stride kernel
 // ---------------------------------------------------------------------------
@@ -237,7 +232,7 @@ __global__ __launch_bounds__(256) void k_small(const uint8_t* __restrict__ arena
 // Static grid-stride over tasks; with the default grid (one task per wave,
 // grid_for(.., 0)) the in-order block dispatcher then acts as the task queue
 // and the tasks in flight form one contiguous window sliding through the arena.
-// Optional XCD grouping (pipck_tune flags bit 3): the dispatcher deals blocks
+// Optional XCD grouping (kXcdGroups): the dispatcher deals blocks
 // round-robin over the 8 XCDs, so blocks with equal blockIdx % 8 share an XCD
 // and each such group can take one contiguous eighth of the tasks (8 windows).
 // Measured: one window is as fast or faster from 38 to 151 GB
@@ -246,9 +241,6 @@ __global__ __launch_bounds__(256) void k_small(const uint8_t* __restrict__ arena
 struct TaskRange {
     uint64_t first, end, step;
 };
-constexpr uint32_t kXcdGroups = 8u;
-constexpr uint32_t kNoPackedTiles = 16u;  // pipck_tune flags bit 4: ragged tiles always take the lookup path
-constexpr uint32_t kWideBlocks = 32u;     // pipck_tune flags bit 5: 4-wave ragged blocks instead of 1-wave
 template <uint32_t WPB = 4>  // waves per block
 __device__ __forceinline__ TaskRange xcd_tasks(uint64_t n_tasks, bool grouped) {
     // wave-uniform as far as the compiler knows too: task addresses feed scalar
@@ -264,12 +256,7 @@ __device__ __forceinline__ TaskRange xcd_tasks(uint64_t n_tasks, bool grouped) {
 // ---------------------------------------------------------------------------
 // per-task timeline (internal measurement, pipck_trace_tasks in pipck_testing.h)
 // ---------------------------------------------------------------------------
-// With tune flags bit 20 the streaming kernels record, per wave task, the
-// 100 MHz wall clock (s_memrealtime) when the task starts and when its results
-// are stored, plus the wave's hardware slot, so tools/task_trace.py can see the
-// launch ramp, the tail, per-XCD progress and the gap between consecutive tasks
-// on one wave slot.  One 32-byte vector store per task; off by default.
-constexpr uint32_t kTrace = 1u << 20;
+// One record per wave task of a launch made with kTrace (pipck_tune.hpp).
 struct TaskTrace {
     uint64_t task, t0, t1, hw;  // hw = XCC_ID << 32 | HW_ID
 };
@@ -358,30 +345,6 @@ __device__ __forceinline__ void trace_task(uint32_t kflags, const TraceBuf& tb, 
 // on gfx9 both count in VM_CNT, so inside the row loop each one would make the
 // next row's wait drain every load in flight.
 constexpr uint32_t kFlatMaxRun = 64;  // packets per wave task
-// tune flags bit 21 (MEASUREMENT ONLY, wrong results): the flat kernel's
-// rows are waited for and consumed by one add each, with no per-packet
-// work, so tools can time the access pattern alone.  (Bits 24..27 are the
-// small kernel's packets per lane: this bit must not overlap them.)
-constexpr uint32_t kLoadsOnly = 1u << 21;
-// tune flags bit 22 (MEASUREMENT ONLY, no results): k_flat skips its task end
-// (the per-packet LDS sums, pseudo-header add and result stores)
-constexpr uint32_t kNoTaskEnd = 1u << 22;
-// bit 23: k_flat's task end computes every result but stores none
-// (MEASUREMENT ONLY, no results)
-constexpr uint32_t kEndNoStore = 1u << 23;
-// bit 28 (same results): the other fixed-stride schedule -- k_flat (one task
-// per wave) instead of the block-cooperative k_flat_coop (pipck_coop.hip),
-// the default for strides from 1 KiB to 64 KiB since round 4
-constexpr uint32_t kFlatAltSchedule = 1u << 28;
-// EXPERIMENTAL (same results): bit 30 = per-wave result stores (the r02 scheme) instead of one coalesced
-// store of the whole block's results by its last wave; bit 31 = wave tasks of
-// exactly the packet count the heuristic names, not rounded to a multiple of 16
-
-constexpr uint32_t kFlatWaveStores = 1u << 30;
-constexpr uint32_t kFlatFreeRun = 1u << 31;
-// bit 30 in k_packed: tile rows on the r02 grid (from the tile's first chunk)
-// instead of the 128-B line grid
-constexpr uint32_t kPackedNoAlign = 1u << 30;
 // u16 slots per lane row: >= run, and an odd number of dwords so the 64 lanes
 // of one ds_write_b16 land in distinct banks (mod 32)
 __host__ __device__ constexpr uint32_t flat_pitch(uint32_t run) {
@@ -823,8 +786,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(flat_waves_
 // row's wait drain the ring).  The lane-per-packet kernels (k_small) spend
 // ~60 VALU per 1 KiB row on per-lane offsets and masks and stall on issue at
 // ~4.2 TB/s; this keeps the VALU work per row to the fold itself.
-constexpr uint32_t kNoFlatTiny = 1u << 17;     // pipck_tune flags bit 17: never k_flat_tiny
-constexpr uint32_t kForceFlatTiny = 1u << 18;  // bit 18: k_flat_tiny without pseudo-headers too
 constexpr uint32_t kFlatTinyMaxHalves = 8;  // strides up to 64 B
 constexpr uint32_t kFlatTinyMaxRun = 2048;  // packets per wave task
 
@@ -972,7 +933,6 @@ constexpr uint32_t kBadSeg = 0x0000FFFFu;
 // lane-per-segment: 1.36 -> 1.69 TB/s on 20-B segments; at 3 chunks (40 B)
 // the chunk stream is 3 % faster (profiles/r01_ragged_shapes6_tiny.jsonl).
 constexpr uint32_t kTinyChunks = 2;
-constexpr uint32_t kNoTinyTiles = 1u << 16;  // pipck_tune flags bit 16: tiny tiles take the chunk stream too
 
 
 // Segment of chunk c: the last segment starting at or before c (which skips
@@ -1086,7 +1046,6 @@ __device__ __forceinline__ void ragged_reduce_row(RaggedTileLds& t, uint32_t row
 // Segment ends a mixed row walks in scalar code; beyond this many the row
 // finds its lanes' segments through LDS start marks instead.
 constexpr uint32_t kRowEndsLoop = 4;
-constexpr uint32_t kPackedMarksOnly = 1u << 19;  // pipck_tune flags bit 19: mixed rows always take the marks (k_packed: the end loop)
 
 // Reduce one row of a packed tile (every segment starts 16-byte aligned where
 // the previous one's chunks end).  Lane i of the wave holds segment i's start
@@ -1479,16 +1438,16 @@ __global__ void k_chain_finish(const uint64_t* __restrict__ seg_begin, const uin
 // ---------------------------------------------------------------------------
 // launch-shape selection
 // ---------------------------------------------------------------------------
+// The tuning words (pipck_testing.h's setters at the end of this file write
+// them); every launch function reads them once, through tune_now().
 struct Tune {
-    std::atomic<uint32_t> lanes{0}, loads{0}, blocks{0}, flags{0};
+    std::atomic<uint32_t> lanes{0}, loads{0}, blocks{0}, flags{0}, ring_mode{0}, probes{0};
 };
 static Tune g_tune;
-bool wave_arm() { return g_tune.lanes.load() == kWaveArm; }
-bool alt_schedule() { return (g_tune.flags.load() >> 28) & 1u; }
-uint32_t g_tune_flags() { return g_tune.flags.load(); }
-uint32_t g_tune_loads() { return g_tune.loads.load(); }
-uint32_t g_tune_blocks() { return g_tune.blocks.load(); }
-std::atomic<uint32_t> g_probes{0};  // pipck_tune_probes (pipck_testing.h)
+TuneView tune_now() {
+    return {g_tune.lanes.load(), g_tune.loads.load(),     g_tune.blocks.load(),
+            g_tune.flags.load(), g_tune.ring_mode.load(), g_tune.probes.load()};
+}
 
 // The batch kernel this thread launched last (pipck_common.hpp, PIPCK_LAUNCH).
 thread_local const void* t_last_kernel = nullptr;
@@ -1518,8 +1477,8 @@ constexpr int kNumVariants = sizeof(kVariants) / sizeof(kVariants[0]);
 // among single-pass shapes take the one wasting the fewest 16-byte lane slots,
 // then the most loads in flight per lane, then the widest group.  Packets too
 // long for any single pass use the widest, deepest shape (fewest passes).
-static const Variant& pick_variant(uint32_t nch) {
-    const uint32_t fl = g_tune.lanes.load(), fn = g_tune.loads.load();
+static const Variant& pick_variant(uint32_t nch, const TuneView& tv) {
+    const uint32_t fl = tv.lanes, fn = tv.loads;
     const Variant* best = nullptr;
     double best_u = -1.0;
     for (const Variant& v : kVariants) {
@@ -1543,7 +1502,6 @@ static const Variant& pick_variant(uint32_t nch) {
     return best ? *best : kVariants[kNumVariants - 1];
 }
 
-constexpr uint32_t kNoSmall = 64u;  // pipck_tune flags bit 6: never the small-packet kernel
 typedef void (*small_fn)(const uint8_t*, uint64_t, uint32_t, uint64_t, const uint32_t*, uint32_t, const uint32_t*,
                          uint64_t, uint16_t*, uint8_t*, uint32_t, uint32_t*);
 struct SmallVariant {
@@ -1556,26 +1514,18 @@ struct SmallVariant {
             {k_small<NL, K, true, false>, k_small<NL, K, true, true>}                              \
     }
 #define PIPCK_S(K) {K, {PIPCK_S1(1, K), PIPCK_S1(2, K), PIPCK_S1(3, K), PIPCK_S1(4, K)}}
-// tune flags bits 24..27 select K (1 = 2, 2 = 4, 3 = 8, 4 = 16); default 2:
-// deeper tasks measured slower (cfg1 at 64M-256M headers: K = 2 / 4 / 8 / 16
-// -> 4.19 / 4.15 / 3.83 / 3.87 TB/s, plain loads beat nt by 10 %,
-// profiles/r01_small_kernel_scan.jsonl)
+// TuneView::small_depth() 1..4 selects K = 2 / 4 / 8 / 16; default 2 (pipck_tune.hpp)
 static const SmallVariant kSmall[] = {PIPCK_S(2), PIPCK_S(4), PIPCK_S(8), PIPCK_S(16)};
 #undef PIPCK_S
 #undef PIPCK_S1
-static const SmallVariant& small_variant() {
-    const uint32_t k = (g_tune.flags.load() >> 24) & 0xFu;  // bits 24..27 (kLoadsOnly is bit 21)
+static const SmallVariant& small_variant(const TuneView& tv) {
+    const uint32_t k = tv.small_depth();
     return kSmall[k >= 1 && k <= 4 ? k - 1 : 0];
 }
-
-constexpr uint32_t kNoFlatSmall = 128u;
-constexpr uint64_t kHdrMinBatch = 8ull << 20;  // headers: k_hdr from here, k_small below  // pipck_tune flags bit 7: never the short-stride flat kernel
 
 // host copies of the XCD-weighted deal's shape (pipck_tune_xcd_weights): kept
 // blocks per period (0 = off) and blocks per XCD per period
 static std::atomic<uint32_t> g_xw_kept{0}, g_xw_period{0};
-
-static bool flat_allowed() { return (g_tune.flags.load() & 2u) == 0; }  // bit 1: never the flat kernel
 
 typedef void (*flat_fn)(const uint8_t*, uint32_t, uint32_t, uint64_t, uint32_t, const uint32_t*, uint32_t,
                         const uint32_t*, uint64_t, uint16_t*, uint8_t*, uint32_t, uint32_t*);
@@ -1592,7 +1542,7 @@ struct FlatVariant {
             {k_flat<U, P, true, false>, k_flat<U, P, true, true>}                         \
         }, (P && (U == 24 || U == 32)) ? k_flat_probe<U, P, false, true> : nullptr        \
     }
-// loads_per_lane 2/4/8/16 = U rows in flight per wave; 3/5/9/13/17/25/33 = ring-pipelined U = 2/4/8/12/16/24/32
+// the ring coding of loads_per_lane (ring_shape, pipck_tune.hpp) without a ring of 6
 // (a ring of 40 or 48 -- 231 / 272 VGPRs -- ran cfg5 1 % / 28 % slower than 32,
 // profiles/r01_flat_one_wave_scan.jsonl, r01_deep_ring_scan.jsonl)
 static const FlatVariant kFlat[] = {PIPCK_F(2, false), PIPCK_F(4, false), PIPCK_F(8, false), PIPCK_F(16, false),
@@ -1607,22 +1557,12 @@ static const flat_fn kFlatSmall[2][2] = {  // [verify][nt]
 static const flat_fn kFlatTiny[3][2][2] = {PIPCK_T(4), PIPCK_T(8), PIPCK_T(16)};  // [ring 4/8/16][verify][nt]
 #undef PIPCK_T
 
-static const FlatVariant& flat_variant(uint32_t loads) {
-    switch (loads) {
-        case 2: return kFlat[0];
-        case 4: return kFlat[1];
-        case 8: return kFlat[2];
-        case 3: return kFlat[4];
-        case 5: return kFlat[5];
-        case 9: return kFlat[6];
-        case 16: return kFlat[3];
-        case 13: return kFlat[7];
-        case 17: return kFlat[8];
-        case 33: return kFlat[9];
-        case 25: return kFlat[10];
-
-        default: return kFlat[2];
-    }
+// the table entry of a shape, or null where the kernel has no such instantiation
+template <class V, size_t N>
+static const V* find_shape(const V (&table)[N], RingShape r) {
+    for (const V& v : table)
+        if ((uint32_t)v.u == r.u && v.pipe == r.pipe) return &v;
+    return nullptr;
 }
 
 // Default grid: blocks_per_cu 256-thread blocks per CU, or (0) one block per
@@ -1631,22 +1571,12 @@ static const FlatVariant& flat_variant(uint32_t loads) {
 // always a contiguous window sliding through the arena (measured best; an
 // explicit atomic queue or a resident-sized grid-stride grid lost 3-15 %,
 // profiles/r01_grid_scan*.jsonl).
-static uint32_t grid_for(uint64_t units_per_block_iter, uint64_t n, uint32_t blocks_per_cu = 8) {
+static uint32_t grid_for(const TuneView& tv, uint64_t units_per_block_iter, uint64_t n, uint32_t blocks_per_cu = 8) {
     uint64_t need = (n + units_per_block_iter - 1) / units_per_block_iter;
-    uint64_t cap = g_tune.blocks.load();
+    uint64_t cap = tv.grid_cap();
     if (!cap) cap = blocks_per_cu ? (uint64_t)device_cus() * blocks_per_cu : 0x7FFFFFFFull;
     if (need > cap) need = cap;
     return (uint32_t)(need ? need : 1);
-}
-
-// Load policy: tune flags bit 0 forces plain loads, bit 2 forces non-temporal
-// ones; otherwise each kernel uses what measured faster on MI355X
-// (profiles/README.md): nt for the streaming kernels, plain for small groups.
-static bool nt_for(bool streaming) {
-    const uint32_t f = g_tune.flags.load();
-    if (f & 1u) return false;
-    if (f & 4u) return true;
-    return streaming;
 }
 
 // bounded: the _n forms (n_flows > 0 with d_pseudo; it bounds every d_flow_of
@@ -1655,6 +1585,7 @@ static bool nt_for(bool streaming) {
 static int launch_fixed(bool verify, const void* d_arena, uint64_t stride, uint32_t len, uint64_t n,
                         const uint32_t* d_pseudo, uint32_t n_flows, const uint32_t* d_flow_of, uint64_t flow_origin,
                         uint16_t* d_out, uint8_t* d_ok, uint32_t* d_err, void* stream, bool bounded) {
+    const TuneView tv = tune_now();
     if (n == 0) return PIPCK_OK;
     if (!d_arena || (verify ? !d_ok : !d_out)) {
         set_error("pipck_checksum_fixed: null arena/output");
@@ -1674,11 +1605,11 @@ static int launch_fixed(bool verify, const void* d_arena, uint64_t stride, uint3
         set_error("pipck_checksum_fixed: stride < len");
         return PIPCK_EINVAL;
     }
-    if (g_tune.lanes.load() == kWaveArm)  // measurement arm: one packet per wave (pipck_wave.hip)
+    if (tv.wave_arm())  // measurement arm: one packet per wave (pipck_wave.hip)
         return launch_wave(verify, false, d_arena, stride, len, nullptr, n, d_pseudo, nf, d_flow_of, flow_origin,
-                           d_out, d_ok, d_err, as_stream(stream), (len + 30u) / 16u, g_tune.loads.load());
+                           d_out, d_ok, d_err, as_stream(stream), (len + 30u) / 16u, tv);
     const bool aligned = ((uintptr_t)d_arena % 16 == 0) && (stride % 16 == 0);
-    if (aligned && flat_allowed() && !g_tune.lanes.load() && stride >= 64 * 16 && stride <= (1ull << 24) &&
+    if (aligned && tv.flat_allowed() && !tv.lanes && stride >= 64 * 16 && stride <= (1ull << 24) &&
         len <= stride) {
         const uint32_t cpp = (uint32_t)(stride / 16);
         // Every stride from 1 KiB to 64 KiB takes the block-cooperative stream
@@ -1692,12 +1623,11 @@ static int launch_fixed(bool verify, const void* d_arena, uint64_t stride, uint3
         // one process, results equal).  At the 1 and 2 KiB strides k_flat
         // measured even to 1.3 % faster on the final build
         // (r04_schedule_ab.jsonl), so those two keep it.  The other schedule
-        // is tune bit 28; strides past 64 KiB always take k_flat.
-        const bool coop = (stride != 1024 && stride != 2048) != ((g_tune.flags.load() & kFlatAltSchedule) != 0);
+        // is kAltSchedule; strides past 64 KiB always take k_flat.
+        const bool coop = (stride != 1024 && stride != 2048) != tv.alt_schedule();
         if (coop && stride <= 65536 &&
             launch_flat_coop(verify, d_arena, stride, len, n, d_pseudo, nf, d_flow_of, flow_origin, d_out, d_ok,
-                             d_err, as_stream(stream), (g_tune.flags.load() >> 8) & 0xFFu, g_tune.loads.load(),
-                             g_tune.flags.load()) == PIPCK_OK)
+                             d_err, as_stream(stream), tv) == PIPCK_OK)
             return PIPCK_OK;
         // Rows in flight per wave and task size.  Jumbo packets (>= 4 KiB, cfg3
         // and cfg5): a ring of 32 rows (191 VGPRs, 2 waves/SIMD) over ~128-row
@@ -1706,10 +1636,10 @@ static int launch_fixed(bool verify, const void* d_arena, uint64_t stride, uint3
         // packets: a ring of 24 over ~64-row tasks (cfg2 +0.7-1.4 % over 16 in
         // three scans; a ring of 32 cost it 8-15 %).  One task per wave either way.
         const bool jumbo = cpp >= 256;
-        const uint32_t flags = g_tune.flags.load();
-        const uint32_t loads = g_tune.loads.load() ? g_tune.loads.load() : (jumbo ? 33u : 25u);
-        const FlatVariant* fv = &flat_variant(loads);
-        const uint32_t rows = (flags >> 8) & 0xFFu ? (flags >> 8) & 0xFFu : (jumbo ? 96u : 46u);
+        // a loads_per_lane outside k_flat's set: 8 rows, not pipelined
+        const FlatVariant* fv = find_shape(kFlat, tv.ring({jumbo ? 32u : 24u, true}, {8, false}));
+        if (!fv) fv = find_shape(kFlat, {8, false});
+        const uint32_t rows = tv.rows() ? tv.rows() : (jumbo ? 96u : 46u);
         uint32_t run = std::min(kFlatMaxRun, std::max<uint32_t>(1u, (64u * rows) / cpp));
         // Shorter packets: a multiple of 16 packets per wave task, so a block's
         // results (4 * run u16) are whole 128-B lines (written once, by the
@@ -1717,26 +1647,27 @@ static int launch_fixed(bool verify, const void* d_arena, uint64_t stride, uint3
         // (profiles/r03_flat_rows_scan.jsonl): cfg2 runs 0.884 ms at 32 packets
         // per task (46.5 rows) against 0.906 at 31 and 0.906 at 48; jumbo
         // packets are best at ~10 packets (96 rows), unrounded.
-        if (!(flags & kFlatFreeRun) && !jumbo && run >= 12) run = std::min(kFlatMaxRun, (run + 8) / 16 * 16);
+        if (!tv.has(kFlatFreeRun) && !jumbo && run >= 12) run = std::min(kFlatMaxRun, (run + 8) / 16 * 16);
         const uint64_t tasks = (n + run - 1) / run;
-        const uint32_t grid = grid_for(4, tasks, 0);
+        const uint32_t grid = grid_for(tv, 4, tasks, 0);
         // per-wave partials + the block's results + its completion counter
         const size_t lds = (4u * 64u * flat_pitch(run) + ((4u * run + 1u) & ~1u)) * sizeof(uint16_t) + 16u;
         // the measurement bits (21-23) run k_flat_probe; the production kernel has them compiled out
-        const bool probe = (flags & (kLoadsOnly | kNoTaskEnd | kEndNoStore)) && fv->probe && !verify && nt_for(true);
+        const bool nt = tv.nt(true);
+        const bool probe = (tv.flags & kProbeBits) && fv->probe && !verify && nt;
         // the XCD-weighted deal (pipck_tune_xcd_weights): ring 24, checksum, nt loads
         const uint32_t xa = g_xw_kept.load();
-        if (xa && !probe && !verify && nt_for(true) && fv->u == 24 && fv->pipe && grid >= 8) {
+        if (xa && !probe && !verify && nt && fv->u == 24 && fv->pipe && grid >= 8) {
             const uint64_t P = 8ull * g_xw_period.load(), periods = (grid + xa - 1) / xa;
             PIPCK_LAUNCH((k_flat_xw<24, true, false, true>), dim3((uint32_t)(periods * P)), dim3(256), lds,
                          as_stream(stream), (const uint8_t*)d_arena, cpp, len, n, run, d_pseudo,
-                         nf, d_flow_of, flow_origin, d_out, d_ok, flags, d_err);
+                         nf, d_flow_of, flow_origin, d_out, d_ok, tv.flags, d_err);
             PIPCK_LAUNCHED("k_flat_xw");
             return PIPCK_OK;
         }
-        PIPCK_LAUNCH(probe ? fv->probe : fv->fn[verify][nt_for(true)], dim3(grid), dim3(256), lds, as_stream(stream),
+        PIPCK_LAUNCH(probe ? fv->probe : fv->fn[verify][nt], dim3(grid), dim3(256), lds, as_stream(stream),
                            (const uint8_t*)d_arena, cpp, len, n, run, d_pseudo, nf, d_flow_of,
-                           flow_origin, d_out, d_ok, flags, d_err);
+                           flow_origin, d_out, d_ok, tv.flags, d_err);
         PIPCK_LAUNCHED("k_flat");
         return PIPCK_OK;
     }
@@ -1744,16 +1675,14 @@ static int launch_fixed(bool verify, const void* d_arena, uint64_t stride, uint3
     // row (uniform 64/128/512-B packets: 6.0/5.8/6.1 TB/s vs 4.5/4.6/5.5 per
     // packet; below 64 B k_small's lane-per-packet is 3-8 % faster,
     // profiles/r01_ragged_shapes3.jsonl)
-    if (aligned && !g_tune.lanes.load() && !(g_tune.flags.load() & kNoFlatSmall) && stride >= 64 && stride < 64 * 16 &&
-        len <= stride) {
+    if (aligned && !tv.lanes && !tv.has(kNoFlatSmall) && stride >= 64 && stride < 64 * 16 && len <= stride) {
         const uint32_t cpp = (uint32_t)(stride / 16);
-        const uint32_t flags = g_tune.flags.load();
-        const uint32_t rows = (flags >> 8) & 0xFFu ? (flags >> 8) & 0xFFu : 64u;
+        const uint32_t rows = tv.rows() ? tv.rows() : 64u;
         const uint32_t run = std::min(kFlatSmallMaxRun, std::max<uint32_t>(1u, (64u * rows) / cpp));
         const uint64_t tasks = (n + run - 1) / run;
-        PIPCK_LAUNCH(kFlatSmall[verify][nt_for(true)], dim3(grid_for(4, tasks, 0)), dim3(256), 0,
+        PIPCK_LAUNCH(kFlatSmall[verify][tv.nt(true)], dim3(grid_for(tv, 4, tasks, 0)), dim3(256), 0,
                            as_stream(stream), (const uint8_t*)d_arena, cpp, len, n, run, d_pseudo,
-                           nf, d_flow_of, flow_origin, d_out, d_ok, flags, d_err);
+                           nf, d_flow_of, flow_origin, d_out, d_ok, tv.flags, d_err);
         PIPCK_LAUNCHED("k_flat_small");
         return PIPCK_OK;
     }
@@ -1762,20 +1691,10 @@ static int launch_fixed(bool verify, const void* d_arena, uint64_t stride, uint3
     // from 8M headers up: 8.6 % faster than k_small at 256M, 6-11 % at 16M-64M,
     // even at 8M, and slower below (1M: 15.3 vs 12.0 us) where k_small's many
     // tiny waves fill the chip sooner (profiles/r03_hdr_scan.jsonl).
-    // pipck_tune loads_per_lane 8/16/24/32 = k_hdr with that ring at any size,
-    // 1 = never k_hdr.
-    {
-        const uint32_t lq = g_tune.loads.load(), flags = g_tune.flags.load();
-        // loads_per_lane 8/16/24/32 = one task per wave with that ring, 9/17/25/33 =
-        // the block-cooperative row order with ring 8/16/24/32
-        const bool force = lq == 8 || lq == 16 || lq == 24 || lq == 32;
-        const bool force_coop = lq == 9 || lq == 17 || lq == 25 || lq == 33;
-        if (!d_pseudo && (stride == 20 || stride == 24) && !g_tune.lanes.load() && lq != 1 &&
-            (force || force_coop || n >= kHdrMinBatch) &&
-            launch_hdr(verify, d_arena, stride, len, n, d_out, d_ok, as_stream(stream), (flags >> 8) & 0xFFu,
-                       force ? lq : (force_coop ? lq - 1 : 0u), nt_for(true), flags, force_coop) == PIPCK_OK)
-            return PIPCK_OK;
-    }
+    // pipck_tune's loads_per_lane forces or forbids it: launch_hdr decodes that.
+    if (!d_pseudo && (stride == 20 || stride == 24) && !tv.lanes &&
+        launch_hdr(verify, d_arena, stride, len, n, d_out, d_ok, as_stream(stream), tv) == PIPCK_OK)
+        return PIPCK_OK;
     // Tiny 8-B-multiple strides with pseudo-headers (pure ACKs, small UDP) or
     // RX verify: the LDS-staged row stream.  cfg1 on 24-B strides, 256M
     // packets: with IPv4 pseudo-headers 1.29 vs 1.40 ms for k_small (+8.5 %),
@@ -1783,21 +1702,19 @@ static int launch_fixed(bool verify, const void* d_arena, uint64_t stride, uint3
     // ran 1.24-1.34 vs 1.22 ms, so it stays on k_small
     // (profiles/r01_flat_tiny_scan.jsonl).
     if ((uintptr_t)d_arena % 16 == 0 && stride % 8 == 0 && stride >= 8 && stride <= 8 * kFlatTinyMaxHalves &&
-        len >= 1 && len <= stride && (d_pseudo || verify || (g_tune.flags.load() & kForceFlatTiny)) &&
-        !g_tune.lanes.load() && !(g_tune.flags.load() & kNoFlatTiny)) {
+        len >= 1 && len <= stride && (d_pseudo || verify || tv.has(kForceFlatTiny)) && !tv.lanes &&
+        !tv.has(kNoFlatTiny)) {
         const uint32_t hpp = (uint32_t)(stride / 8);
-        const uint32_t flags = g_tune.flags.load();
-        const uint32_t lq = g_tune.loads.load();
-        const int ui = lq == 8 ? 1 : (lq == 16 ? 2 : 0);  // ring of 4 rows by default
-        const uint32_t rows = (flags >> 8) & 0xFFu ? (flags >> 8) & 0xFFu : 12u;
+        const int ui = tv.loads == 8 ? 1 : (tv.loads == 16 ? 2 : 0);  // ring of 4 rows by default
+        const uint32_t rows = tv.rows() ? tv.rows() : 12u;
         // whole LDS groups per task (so tasks start 1 KiB aligned), ~`rows` rows
         const uint32_t G = tiny_group_rows(hpp), P = G * 128u / hpp;
         const uint32_t run = std::max(1u, std::min(kFlatTinyMaxRun / P, rows / G)) * P;
         const uint64_t tasks = (n + run - 1) / run;
         const size_t lds = 4u * tiny_wave_lds(hpp, run);
-        PIPCK_LAUNCH(kFlatTiny[ui][verify][nt_for(true)], dim3(grid_for(4, tasks, 0)), dim3(256), lds,
+        PIPCK_LAUNCH(kFlatTiny[ui][verify][tv.nt(true)], dim3(grid_for(tv, 4, tasks, 0)), dim3(256), lds,
                            as_stream(stream), (const uint8_t*)d_arena, hpp, len, n, run, d_pseudo,
-                           nf, d_flow_of, flow_origin, d_out, d_ok, flags, d_err);
+                           nf, d_flow_of, flow_origin, d_out, d_ok, tv.flags, d_err);
         PIPCK_LAUNCHED("k_flat_tiny");
         return PIPCK_OK;
     }
@@ -1807,113 +1724,86 @@ static int launch_fixed(bool verify, const void* d_arena, uint64_t stride, uint3
     while (g > 1 && stride % g) g >>= 1;
     const uint32_t hmax = (uint32_t)((uintptr_t)d_arena % g) + 16u - g;
     const uint32_t small_nl = (hmax + len + 15u) / 16u;
-    if (!g_tune.lanes.load() && !(g_tune.flags.load() & kNoSmall) && small_nl <= 4) {
-        const SmallVariant& sv = small_variant();
+    if (!tv.lanes && !tv.has(kNoSmall) && small_nl <= 4) {
+        const SmallVariant& sv = small_variant(tv);
         const uint64_t waves = (n + 64u * sv.k - 1) / (64u * sv.k);
-        PIPCK_LAUNCH(sv.fn[small_nl ? small_nl - 1 : 0][verify][nt_for(false)], dim3((uint32_t)((waves + 3) / 4)), dim3(256), 0,
-                           as_stream(stream), (const uint8_t*)d_arena, stride, len, n, d_pseudo,
-                           nf, d_flow_of, flow_origin, d_out, d_ok, g_tune.flags.load(), d_err);
+        PIPCK_LAUNCH(sv.fn[small_nl ? small_nl - 1 : 0][verify][tv.nt(false)], dim3((uint32_t)((waves + 3) / 4)),
+                     dim3(256), 0, as_stream(stream), (const uint8_t*)d_arena, stride, len, n, d_pseudo, nf, d_flow_of,
+                     flow_origin, d_out, d_ok, tv.flags, d_err);
         PIPCK_LAUNCHED("k_small");
         return PIPCK_OK;
     }
     const uint32_t nch = (len + (aligned ? 0u : 15u) + 15u) / 16u;
-    const Variant& v = pick_variant(nch);
-    const uint32_t grid = grid_for(256 / v.g, n);
-    PIPCK_LAUNCH(v.fn[verify][nt_for(false)], dim3(grid), dim3(256), 0, as_stream(stream), (const uint8_t*)d_arena,
+    const Variant& v = pick_variant(nch, tv);
+    const uint32_t grid = grid_for(tv, 256 / v.g, n);
+    PIPCK_LAUNCH(v.fn[verify][tv.nt(false)], dim3(grid), dim3(256), 0, as_stream(stream), (const uint8_t*)d_arena,
                        stride, len, n, d_pseudo, nf, d_flow_of, flow_origin, d_out, d_ok, d_err);
     PIPCK_LAUNCHED("k_fixed");
     return PIPCK_OK;
 }
 
-template <bool FINAL, int U, bool PIPE, bool NT>
-static void launch_ragged_k(bool wide, uint64_t tiles, hipStream_t s, const uint8_t* a, const pipck_desc* d,
-                            uint64_t n, const uint32_t* ps, uint16_t* out, uint32_t* fseg, uint8_t* ok, uint32_t* err,
-                            uint32_t f, uint64_t ab, uint32_t nf) {
-    // one tile per wave: the in-order dispatcher hands out tiles as waves finish
-    // (measured best, profiles/r01_size_scan*.jsonl)
-    // (runs of 2-4 consecutive tiles per wave measured 2-5 % slower,
-    // profiles/r01_ragged_tpw_scan.jsonl)
-    if (wide)
-        PIPCK_LAUNCH((k_ragged<FINAL, U, PIPE, NT, 4>), dim3(grid_for(4, tiles, 0)),
-                           dim3(256), 0, s, a, d, n, ps, out, fseg, ok, err, f, ab, nf);
-    else
-        PIPCK_LAUNCH((k_ragged<FINAL, U, PIPE, NT, 1>), dim3(grid_for(1, tiles, 0)),
-                           dim3(64), 0, s, a, d, n, ps, out, fseg, ok, err, f, ab, nf);
-}
-
-template <int U, bool PIPE>
-static void launch_ragged_u(bool final_, bool nt, uint64_t tiles, hipStream_t s, const uint8_t* a,
-                            const pipck_desc* d, uint64_t n, const uint32_t* ps, uint16_t* out, uint32_t* fseg,
-                            uint8_t* ok, uint32_t* err, uint64_t ab, uint32_t nf) {
-    const uint32_t f = g_tune.flags.load();
-    const bool wide = (f & kWideBlocks) != 0;
-    if (final_) {
-        if (nt) launch_ragged_k<true, U, PIPE, true>(wide, tiles, s, a, d, n, ps, out, fseg, ok, err, f, ab, nf);
-        else launch_ragged_k<true, U, PIPE, false>(wide, tiles, s, a, d, n, ps, out, fseg, ok, err, f, ab, nf);
-    } else {
-        if (nt) launch_ragged_k<false, U, PIPE, true>(wide, tiles, s, a, d, n, ps, out, fseg, ok, err, f, ab, nf);
-        else launch_ragged_k<false, U, PIPE, false>(wide, tiles, s, a, d, n, ps, out, fseg, ok, err, f, ab, nf);
-    }
-}
+typedef void (*ragged_fn)(const uint8_t*, const pipck_desc*, uint64_t, const uint32_t*, uint16_t*, uint32_t*, uint8_t*,
+                          uint32_t*, uint32_t, uint64_t, uint32_t);
+struct RaggedVariant {
+    int u;
+    bool pipe;
+    ragged_fn fn[2][2][2];  // [chain partials][plain loads][1-wave blocks]
+};
+#define PIPCK_R1(FIN, U, P) \
+    { {k_ragged<FIN, U, P, true, 4>, k_ragged<FIN, U, P, true, 1>}, {k_ragged<FIN, U, P, false, 4>, k_ragged<FIN, U, P, false, 1>} }
+#define PIPCK_R(U, P) {U, P, {PIPCK_R1(true, U, P), PIPCK_R1(false, U, P)}}
+// The ring coding of loads_per_lane (ring_shape, pipck_tune.hpp), every shape
+// of it.  (Entries and indices are in the order the kernels have always been
+// instantiated in, which is the order the compiler lays them out in the code
+// object: the device code stays byte for byte what it was.)
+static const RaggedVariant kRagged[] = {PIPCK_R(2, false), PIPCK_R(4, false), PIPCK_R(8, false), PIPCK_R(16, false),
+                                        PIPCK_R(2, true),  PIPCK_R(8, true),  PIPCK_R(6, true),  PIPCK_R(12, true),
+                                        PIPCK_R(16, true), PIPCK_R(24, true), PIPCK_R(32, true), PIPCK_R(4, true)};
+#undef PIPCK_R
+#undef PIPCK_R1
 
 // arena_bytes / n_flows bound every descriptor (UINT64_MAX / UINT32_MAX: trusted)
 static int launch_ragged(bool final_, const void* d_arena, const pipck_desc* d_desc, uint64_t n,
                          const uint32_t* d_pseudo, uint16_t* d_out, uint32_t* d_fseg, uint8_t* d_ok, uint32_t* d_err,
                          hipStream_t s, uint64_t arena_bytes, uint32_t n_flows) {
-    if (final_ && !d_fseg && g_tune.lanes.load() == kWaveArm)  // measurement arm: one packet per wave
+    const TuneView tv = tune_now();
+    if (final_ && !d_fseg && tv.wave_arm())  // measurement arm: one packet per wave
         return launch_wave(d_ok != nullptr, true, d_arena, 0, 0, d_desc, n, d_pseudo, n_flows, nullptr, 0, d_out, d_ok,
-                           d_err, s, 0, g_tune.loads.load() ? g_tune.loads.load() : 4u, arena_bytes);
+                           d_err, s, 0, tv, arena_bytes);
     const uint64_t tiles = (n + 63) / 64;
-    // loads_per_lane: 2/4/8/16 rows in flight on packed tiles (at most 4 on
-    // others), 3/5/7/9/13/17/25/33 = ring-pipelined 2/4/6/8/12/16/24/32.
-    // Default: ring of 24 (cfg4: ring 12 +2.5 % over plain 4,
-    // profiles/r01_ragged_ring_scan.jsonl; ring 24 +1.4 % over 12/16 and ring
-    // 32 -14 %, r01_deep_ring_scan.jsonl)
-    const uint32_t u = g_tune.loads.load() ? g_tune.loads.load() : 25u;
-    const bool nt = nt_for(true);
-    const uint8_t* a = (const uint8_t*)d_arena;
-    switch (u) {
-        case 2: launch_ragged_u<2, false>(final_, nt, tiles, s, a, d_desc, n, d_pseudo, d_out, d_fseg, d_ok, d_err, arena_bytes, n_flows); break;
-        case 4: launch_ragged_u<4, false>(final_, nt, tiles, s, a, d_desc, n, d_pseudo, d_out, d_fseg, d_ok, d_err, arena_bytes, n_flows); break;
-        case 8: launch_ragged_u<8, false>(final_, nt, tiles, s, a, d_desc, n, d_pseudo, d_out, d_fseg, d_ok, d_err, arena_bytes, n_flows); break;
-        case 16: launch_ragged_u<16, false>(final_, nt, tiles, s, a, d_desc, n, d_pseudo, d_out, d_fseg, d_ok, d_err, arena_bytes, n_flows); break;
-        case 3: launch_ragged_u<2, true>(final_, nt, tiles, s, a, d_desc, n, d_pseudo, d_out, d_fseg, d_ok, d_err, arena_bytes, n_flows); break;
-        case 9: launch_ragged_u<8, true>(final_, nt, tiles, s, a, d_desc, n, d_pseudo, d_out, d_fseg, d_ok, d_err, arena_bytes, n_flows); break;
-        case 7: launch_ragged_u<6, true>(final_, nt, tiles, s, a, d_desc, n, d_pseudo, d_out, d_fseg, d_ok, d_err, arena_bytes, n_flows); break;
-        case 13: launch_ragged_u<12, true>(final_, nt, tiles, s, a, d_desc, n, d_pseudo, d_out, d_fseg, d_ok, d_err, arena_bytes, n_flows); break;
-        case 17: launch_ragged_u<16, true>(final_, nt, tiles, s, a, d_desc, n, d_pseudo, d_out, d_fseg, d_ok, d_err, arena_bytes, n_flows); break;
-        case 25: launch_ragged_u<24, true>(final_, nt, tiles, s, a, d_desc, n, d_pseudo, d_out, d_fseg, d_ok, d_err, arena_bytes, n_flows); break;
-        case 33: launch_ragged_u<32, true>(final_, nt, tiles, s, a, d_desc, n, d_pseudo, d_out, d_fseg, d_ok, d_err, arena_bytes, n_flows); break;
-        default: launch_ragged_u<4, true>(final_, nt, tiles, s, a, d_desc, n, d_pseudo, d_out, d_fseg, d_ok, d_err, arena_bytes, n_flows); break;
-    }
+    // Rows in flight on packed tiles (at most 4 on others).  Default: ring of
+    // 24 (cfg4: ring 12 +2.5 % over plain 4, profiles/r01_ragged_ring_scan.jsonl;
+    // ring 24 +1.4 % over 12/16 and ring 32 -14 %, r01_deep_ring_scan.jsonl); a
+    // loads_per_lane outside the coding: ring of 4
+    const RaggedVariant* rv = find_shape(kRagged, tv.ring({24, true}, {4, true}));
+    // one tile per wave: the in-order dispatcher hands out tiles as waves finish
+    // (measured best, profiles/r01_size_scan*.jsonl)
+    // (runs of 2-4 consecutive tiles per wave measured 2-5 % slower,
+    // profiles/r01_ragged_tpw_scan.jsonl)
+    const bool wide = tv.has(kWideBlocks);
+    PIPCK_LAUNCH(rv->fn[!final_][!tv.nt(true)][!wide], dim3(grid_for(tv, wide ? 4 : 1, tiles, 0)),
+                 dim3(wide ? 256 : 64), 0, s, (const uint8_t*)d_arena, d_desc, n, d_pseudo, d_out, d_fseg, d_ok, d_err,
+                 tv.flags, arena_bytes, n_flows);
     PIPCK_LAUNCHED("k_ragged");
     return PIPCK_OK;
 }
 
-template <bool V, int U>
-static void launch_packed_u(bool nt, uint64_t tiles, hipStream_t s, const uint8_t* a, const uint16_t* lens,
-                            const uint64_t* tc, uint64_t n, const uint32_t* ps, uint32_t nf, const uint32_t* fo,
-                            uint64_t origin, uint16_t* out, uint8_t* ok, uint32_t f, uint64_t ach, uint32_t* err) {
-    const bool marks = (f & kPackedMarksOnly) != 0;
-    if (nt && marks)
-        PIPCK_LAUNCH((k_packed<V, U, true, true>), dim3((uint32_t)tiles), dim3(64), 0, s, a, lens, tc, n, ps, nf,
-                           fo, origin, out, ok, f, ach, err);
-    else if (nt)
-        PIPCK_LAUNCH((k_packed<V, U, true, false>), dim3((uint32_t)tiles), dim3(64), 0, s, a, lens, tc, n, ps, nf,
-                           fo, origin, out, ok, f, ach, err);
-    else if (marks)
-        PIPCK_LAUNCH((k_packed<V, U, false, true>), dim3((uint32_t)tiles), dim3(64), 0, s, a, lens, tc, n, ps, nf,
-                           fo, origin, out, ok, f, ach, err);
-    else
-        PIPCK_LAUNCH((k_packed<V, U, false, false>), dim3((uint32_t)tiles), dim3(64), 0, s, a, lens, tc, n, ps, nf,
-                           fo, origin, out, ok, f, ach, err);
-}
+typedef void (*packed_fn)(const uint8_t*, const uint16_t*, const uint64_t*, uint64_t, const uint32_t*, uint32_t,
+                          const uint32_t*, uint64_t, uint16_t*, uint8_t*, uint32_t, uint64_t, uint32_t*);
+#define PIPCK_P1(V, U) \
+    { {k_packed<V, U, true, true>, k_packed<V, U, true, false>}, {k_packed<V, U, false, true>, k_packed<V, U, false, false>} }
+#define PIPCK_P(U) {PIPCK_P1(true, U), PIPCK_P1(false, U)}
+// [ring 16/24/32][checksum][plain loads][end loop] (in instantiation order, as kRagged)
+static const packed_fn kPacked[3][2][2][2] = {PIPCK_P(16), PIPCK_P(24), PIPCK_P(32)};
+#undef PIPCK_P
+#undef PIPCK_P1
 
 // bounded: the _n forms (flow_of entries bounded by n_flows when it is given)
 static int launch_packed(bool verify, const void* d_arena, uint64_t arena_bytes, const uint16_t* d_lens,
                          const uint64_t* d_tile_chunk, uint64_t n, const uint32_t* d_pseudo, uint32_t n_flows,
                          const uint32_t* d_flow_of, uint64_t flow_origin, uint16_t* d_out, uint8_t* d_ok,
                          uint32_t* d_err, hipStream_t s, bool bounded = true) {
+    const TuneView tv = tune_now();
     if (n == 0) return PIPCK_OK;
     if (!d_arena || !d_lens || !d_tile_chunk || (verify ? !d_ok : !d_out)) {
         set_error("pipck_checksum_packed: null pointer");
@@ -1934,28 +1824,19 @@ static int launch_packed(bool verify, const void* d_arena, uint64_t arena_bytes,
     }
     // whole 16-byte chunks the kernel may read: the arena's bytes rounded up to 16
     const uint64_t ach = arena_bytes / 16 + (arena_bytes % 16 ? 1u : 0u);
-    // Mixed rows take the LDS-marks path by default here (tune flags bit 19
+    // Mixed rows take the LDS-marks path by default here (kPackedMarksOnly
     // selects the scalar end loop instead, the reverse of k_ragged), with a
     // ring of 32 rows (154 VGPRs, still 3 waves/SIMD): cfg4 1.2618 vs 1.2814 ms and, at 16M
     // packets, 2.448 vs 2.518 ms against the ring of 24 with the end loop, each
     // alone gaining less (profiles/r02_knob_scan_cfg4_packed.jsonl).
-    const uint32_t f = g_tune.flags.load() ^ kPackedMarksOnly;
-    const bool nt = nt_for(true);
-    const uint8_t* a = (const uint8_t*)d_arena;
+    const uint32_t f = tv.flags ^ kPackedMarksOnly;
     // the kernel's n_flows: the modulus without flow_of; with it, the bound of its entries
     const uint32_t nf = d_flow_of ? (bounded && n_flows ? n_flows : UINT32_MAX) : (n_flows ? n_flows : 1u);
-    // rows in flight per wave: 17/25/33 = rings of 16/24/32
-    switch (g_tune.loads.load()) {
-        case 17: verify ? launch_packed_u<true, 16>(nt, tiles, s, a, d_lens, d_tile_chunk, n, d_pseudo, nf, d_flow_of, flow_origin, d_out, d_ok, f, ach, d_err)
-                        : launch_packed_u<false, 16>(nt, tiles, s, a, d_lens, d_tile_chunk, n, d_pseudo, nf, d_flow_of, flow_origin, d_out, d_ok, f, ach, d_err);
-                 break;
-        case 25: verify ? launch_packed_u<true, 24>(nt, tiles, s, a, d_lens, d_tile_chunk, n, d_pseudo, nf, d_flow_of, flow_origin, d_out, d_ok, f, ach, d_err)
-                        : launch_packed_u<false, 24>(nt, tiles, s, a, d_lens, d_tile_chunk, n, d_pseudo, nf, d_flow_of, flow_origin, d_out, d_ok, f, ach, d_err);
-                 break;
-        default: verify ? launch_packed_u<true, 32>(nt, tiles, s, a, d_lens, d_tile_chunk, n, d_pseudo, nf, d_flow_of, flow_origin, d_out, d_ok, f, ach, d_err)
-                        : launch_packed_u<false, 32>(nt, tiles, s, a, d_lens, d_tile_chunk, n, d_pseudo, nf, d_flow_of, flow_origin, d_out, d_ok, f, ach, d_err);
-                 break;
-    }
+    // rows in flight per wave: loads_per_lane 17/25 = rings of 16/24, anything else 32
+    const int ui = tv.loads == 17 ? 0 : (tv.loads == 25 ? 1 : 2);
+    PIPCK_LAUNCH(kPacked[ui][!verify][!tv.nt(true)][!(f & kPackedMarksOnly)], dim3((uint32_t)tiles), dim3(64), 0, s,
+                 (const uint8_t*)d_arena, d_lens, d_tile_chunk, n, d_pseudo, nf, d_flow_of, flow_origin, d_out, d_ok, f,
+                 ach, d_err);
     PIPCK_LAUNCHED("k_packed");
     return PIPCK_OK;
 }
@@ -2019,7 +1900,9 @@ int pipck_last_launch(char* buf, size_t cap) {
     return rc;
 }
 
-void pipck_tune_probes(uint32_t probes) { g_probes.store(probes); }
+void pipck_tune_probes(uint32_t probes) { g_tune.probes.store(probes); }
+
+void pipck_tune_ring(uint32_t mode) { g_tune.ring_mode.store(mode); }
 
 int pipck_tune_xcd_weights(const uint32_t* m, uint32_t period) {
     uint32_t w[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
@@ -2042,7 +1925,7 @@ int pipck_tune_xcd_weights(const uint32_t* m, uint32_t period) {
 
 int pipck_trace_tasks(void* d_buf, uint64_t cap) {
     // d_buf: device memory for cap 32-byte records (null: off); the tasks of a
-    // launch made with tune flags bit 20 land at their task index
+    // launch made with kTrace land at their task index
     TaskTrace* p = (TaskTrace*)d_buf;
     const uint64_t c = d_buf ? cap : 0;
     PIPCK_HIP(hipMemcpyToSymbol(HIP_SYMBOL(g_trace), &p, sizeof p));

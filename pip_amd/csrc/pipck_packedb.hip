@@ -398,8 +398,8 @@ __global__ __launch_bounds__(64 * W) void k_packedb_tx(uint8_t* arena, const uin
 // ring of 8 (1.205-1.209 ms against 1.328-1.336 for one wave, 1.259 for 8
 // waves: its tile ends with one wave judging 64 frames, which a narrower block
 // overlaps better).
-static int packedb_shape(bool rx) {
-    switch (g_tune_loads()) {
+static int packedb_shape(bool rx, const TuneView& tv) {
+    switch (tv.loads) {
         case 32: return 132;
         case 48: return 408;
         case 28: return rx ? 216 : 803;
@@ -477,7 +477,7 @@ static int launch_packedb(bool verify, const void* d_arena, uint64_t arena_bytes
                          d_lens, d_tile_off, n, d_pseudo, nf, d_flow_of, flow_origin, d_out, d_ok, arena_bytes,   \
                          d_err);                                                                               \
         break
-    switch (packedb_shape(false)) {  // non-temporal loads throughout, as k_packed
+    switch (packedb_shape(false, tune_now())) {  // non-temporal loads throughout, as k_packed
         PIPCK_PB(1, 32);
         PIPCK_PB(4, 8);
         PIPCK_PB(8, 2);
@@ -514,7 +514,7 @@ int launch_packedb_rx(const void* d_arena, uint64_t arena_bytes, const uint16_t*
         PIPCK_LAUNCH((k_packedb_rx<UU, true, WW>), dim3((uint32_t)tiles), dim3(64 * WW), 0, s, a, d_lens,       \
                      d_tile_off, n, d_ok, arena_bytes, d_err);                                                 \
         break
-    switch (packedb_shape(true)) {
+    switch (packedb_shape(true, tune_now())) {
         PIPCK_PBRX(1, 32);
         PIPCK_PBRX(2, 16);
         default:
@@ -554,7 +554,7 @@ int launch_packedb_tx(void* d_arena, uint64_t arena_bytes, const uint16_t* d_len
         PIPCK_LAUNCH((k_packedb_tx<UU, true, WW>), dim3((uint32_t)tiles), dim3(64 * WW), 0, s, a, d_lens,       \
                      d_tile_off, n, flags, d_done, arena_bytes, d_err);                                        \
         break
-    switch (packedb_shape(true)) {
+    switch (packedb_shape(true, tune_now())) {
         PIPCK_PBTX(1, 32);
         PIPCK_PBTX(2, 16);
         default:

@@ -316,15 +316,8 @@ __global__ __launch_bounds__(256) void k_ring_slots(const uint8_t* __restrict__ 
 // rx_from_window, so one wave's parse is spread over 64 slots.
 constexpr uint32_t kRingB = 64;        // slots per block
 constexpr uint32_t kRingCoopRows = 2;  // mean rows per slot from which the waves interleave
-// pipck_tune_ring (pipck_testing.h): k_ring's schedule switches, a word of their
-// own (they once shared pipck_tune's flag bits 27 / 29 with the
-// small kernel's depth and the result-store policy)
-constexpr uint32_t kRingOwnSlots = 1u;  // the row stream never interleaves its waves
-constexpr uint32_t kRingAllCoop = 2u;   // the row stream always interleaves them
-constexpr uint32_t kRingNoAdapt = 4u;   // no feedback: k_ring at every fill (the round-5 default)
-constexpr uint32_t kRingAdaptAll = 8u;  // the feedback at every slot stride (tests; default from 4 KiB)
+// (k_ring's `kflags` is pipck_tune_ring's mode word: kRing* in pipck_tune.hpp)
 constexpr uint64_t kAdaptMinStride = 4096;  // jumbo slots: below, k_ring wins at every fill
-std::atomic<uint32_t> g_ring_mode{0};
 
 struct RingLds {
     u32x4 hdr[6][kRingB];  // chunk k of slot g's header window
@@ -595,13 +588,14 @@ int launch_ring_rx(const void* d_arena, uint64_t stride, const uint16_t* d_lens,
         return PIPCK_EINVAL;
     }
     const uint32_t cpp = (uint32_t)(stride / 16);
-    const uint32_t flags = g_ring_mode.load();
+    const TuneView tv = tune_now();
+    const uint32_t flags = tv.ring_mode;
     // jumbo slots: k_ring or the row stream, by the feedback of this ring's
     // earlier launches (speed only, the verdicts are the same)
     RingFb fb{nullptr, nullptr, 1u, 0u, 0u};
     bool rows = false;
     hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-    if (!wave_arm() && !alt_schedule() && !(flags & kRingNoAdapt) &&
+    if (!tv.wave_arm() && !tv.alt_schedule() && !(flags & kRingNoAdapt) &&
         (stride >= kAdaptMinStride || (flags & kRingAdaptAll)) &&
         hipStreamIsCapturing(s, &cap) == hipSuccess && cap == hipStreamCaptureStatusNone) {
         // (a stream being captured into a graph gets k_ring: the feedback's first
@@ -609,7 +603,7 @@ int launch_ring_rx(const void* d_arena, uint64_t stride, const uint16_t* d_lens,
         const int rc = ring_feedback(d_arena, stride, s, &fb, &rows);
         if (rc) return rc;
     }
-    if (wave_arm()) {  // measurement arm: slot by slot, a wave per slot
+    if (tv.wave_arm()) {  // measurement arm: slot by slot, a wave per slot
         const uint64_t blocks = (n + 4u * kSlotG - 1) / (4u * kSlotG);
         if (blocks > 0x7FFFFFFFull) {
             set_error("pipck_rx_verify_ring: too many slots for one launch");
@@ -620,7 +614,7 @@ int launch_ring_rx(const void* d_arena, uint64_t stride, const uint16_t* d_lens,
         PIPCK_LAUNCHED("k_ring_slots");
         return PIPCK_OK;
     }
-    if (alt_schedule() || rows) {  // the row stream over whole slots (dense jumbo rings; tune bit 28: always)
+    if (tv.alt_schedule() || rows) {  // the row stream over whole slots (dense jumbo rings; tune bit 28: always)
         // K slots per block task: ~4 waves x 48 rows (x 64 for jumbo slots), a
         // multiple of 8, at most 256 (one slot per thread at the end) -- k_flat_coop's
         uint32_t K = (4u * (cpp >= 256 ? 64u : 48u) * 64u) / cpp;
@@ -652,7 +646,7 @@ int launch_ring_rx(const void* d_arena, uint64_t stride, const uint16_t* d_lens,
     // tune's blocks knob, 8 / 16 / 32): sub-groups helped jumbo slots only with a
     // ring of 24 (0.890 against 0.879 of peak) and drain a shallow ring between
     // groups of short slots (full 1.5 KiB slots 2.46 against 1.86 ms)
-    const uint32_t gt = g_tune_blocks();
+    const uint32_t gt = tv.blocks;
     const uint32_t G = (gt == 8 || gt == 16 || gt == 32) ? gt : 64u;
     if (blocks > 0x7FFFFFFFull) {
         set_error("pipck_rx_verify_ring: too many slots for one launch");
@@ -666,7 +660,7 @@ int launch_ring_rx(const void* d_arena, uint64_t stride, const uint16_t* d_lens,
 #define PIPCK_RING(UU, UUD)                                                                                     \
     PIPCK_LAUNCH((k_ring<UU, UUD>), dim3((uint32_t)blocks), dim3(256), 0, s, a, st, d_lens, n, G, d_ok, d_err,    \
                  flags, fb)
-    switch (g_tune_loads()) {
+    switch (tv.loads) {
         case 8: PIPCK_RING(8, 8); break;
         case 12: PIPCK_RING(12, 12); break;
         case 16: PIPCK_RING(16, 16); break;
@@ -683,8 +677,6 @@ int launch_ring_rx(const void* d_arena, uint64_t stride, const uint16_t* d_lens,
 }  // namespace pipck
 
 extern "C" {
-
-void pipck_tune_ring(uint32_t mode) { pipck::g_ring_mode.store(mode); }
 
 int pipck_rx_verify_ring_n(const void* d_arena, uint64_t slot_stride, const uint16_t* d_lens, uint64_t n,
                            uint8_t* d_ok, uint32_t* d_err, void* stream) {

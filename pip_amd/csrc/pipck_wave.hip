@@ -89,17 +89,17 @@ typedef void (*wave_fn)(const uint8_t*, uint64_t, uint32_t, const pipck_desc*, u
 // loads per lane per pass: 2 for packets up to 2 KiB, 4 above (cfg3 / cfg5 at
 // 4: 0.85 / 0.84 of HBM peak against 0.71-0.73 / 0.69-0.71 at 8 and 16, which
 // cover a jumbo packet in one pass; profiles/r04_wave_per_packet_ab.jsonl), or
-// the caller's override
+// the tune's loads_per_lane; descriptor batches (lengths unknown here) take 4
 int launch_wave(bool verify, bool desc, const void* d_arena, uint64_t stride, uint32_t len, const pipck_desc* d_desc,
                 uint64_t n, const uint32_t* d_pseudo, uint32_t n_flows, const uint32_t* d_flow_of,
                 uint64_t flow_origin, uint16_t* d_out, uint8_t* d_ok, uint32_t* d_err, hipStream_t s,
-                uint32_t max_chunks, uint32_t nl, uint64_t arena_bytes) {
+                uint32_t max_chunks, const TuneView& tv, uint64_t arena_bytes) {
     static const wave_fn kWave[4][2][2] = {  // [NL 2/4/8/16][verify][desc]
         {{k_wave<2, false, false>, k_wave<2, false, true>}, {k_wave<2, true, false>, k_wave<2, true, true>}},
         {{k_wave<4, false, false>, k_wave<4, false, true>}, {k_wave<4, true, false>, k_wave<4, true, true>}},
         {{k_wave<8, false, false>, k_wave<8, false, true>}, {k_wave<8, true, false>, k_wave<8, true, true>}},
         {{k_wave<16, false, false>, k_wave<16, false, true>}, {k_wave<16, true, false>, k_wave<16, true, true>}}};
-    if (!nl) nl = max_chunks <= 128 ? 2u : 4u;
+    const uint32_t nl = tv.loads ? tv.loads : (desc || max_chunks > 128 ? 4u : 2u);
     const int ni = nl >= 16 ? 3 : (nl >= 8 ? 2 : (nl >= 4 ? 1 : 0));
     const uint64_t blocks = (n + 3) / 4;
     if (blocks > 0x7FFFFFFFull) {

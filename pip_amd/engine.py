@@ -590,6 +590,22 @@ def gen_rx_frames(n: int, seed: int, checksummed: bool = True, l4_len: int = 0):
     return arena, lens, tile_off, kind, start, l4
 
 
+# The layout of pipck_tune's flags word, as tune() spells it: keyword -> bit.  The one place that
+# defines the layout is pip_amd/csrc/pipck_tune.hpp; tests/test_tune_layout.py holds this copy to it.
+TUNE_BITS = {
+    "plain_loads": 0, "nt_loads": 2, "xcd_groups": 3, "wide_blocks": 5, "force_flat_tiny": 18,
+    "packed_marks_only": 19, "trace": 20, "loads_only": 21, "no_task_end": 22, "end_no_store": 23,
+    "alt_flat_schedule": 28, "plain_result_stores": 29, "wave_stores": 30, "packed_no_align": 30, "free_run": 31,
+}
+TUNE_INVERTED_BITS = {  # keywords that default to True and set their bit when False
+    "flat": 1, "packed_tiles": 4, "small": 6, "flat_small": 7, "tiny_tiles": 16, "flat_tiny": 17,
+}
+TUNE_FIELDS = {"rows_per_task": (8, 8), "small_k_log": (24, 4)}  # keyword -> (shift, width)
+TUNE_RING_BITS = {"ring_own_slots": 0, "ring_all_coop": 1}       # pipck_tune_ring's word
+TUNE_RING_ADAPT = {None: 0, False: 1 << 2, True: 1 << 3}         # ring_adapt: no feedback / feedback at every stride
+TUNE_PROBE_BITS = {"hdr_in_place": 0}                            # pipck_tune_probes' word
+
+
 def tune(lanes_per_packet: int = 0, loads_per_lane: int = 0, blocks: int = 0, plain_loads: bool = False,
          flat: bool = True, nt_loads: bool = False, rows_per_task: int = 0, xcd_groups: bool = False,
          packed_tiles: bool = True, wide_blocks: bool = False,
@@ -612,17 +628,16 @@ def tune(lanes_per_packet: int = 0, loads_per_lane: int = 0, blocks: int = 0, pl
     27 / 29 with small_k_log and plain_result_stores)."""
     if not 0 <= small_k_log <= 4:
         raise ValueError("small_k_log must be 0..4")
-    flags = ((1 if plain_loads else 0) | (0 if flat else 2) | (4 if nt_loads else 0) | (8 if xcd_groups else 0)
-             | (0 if packed_tiles else 16) | (32 if wide_blocks else 0) | (0 if small else 64)
-             | (0 if flat_small else 128) | (rows_per_task << 8) | (0 if tiny_tiles else 1 << 16)
-             | (0 if flat_tiny else 1 << 17) | (1 << 18 if force_flat_tiny else 0) | (small_k_log << 24)
-             | (1 << 19 if packed_marks_only else 0) | (1 << 20 if trace else 0) | (1 << 21 if loads_only else 0) | (1 << 22 if no_task_end else 0)
-             | (1 << 23 if end_no_store else 0) | (1 << 28 if alt_flat_schedule else 0)
-             | (1 << 29 if plain_result_stores else 0)
-             | (1 << 30 if (wave_stores or packed_no_align) else 0)
-             | (1 << 31 if free_run else 0))
+    kw = locals()
+    flags = 0
+    for name, bit in TUNE_BITS.items():
+        flags |= (1 << bit) if kw[name] else 0
+    for name, bit in TUNE_INVERTED_BITS.items():
+        flags |= 0 if kw[name] else (1 << bit)
+    for name, (shift, _width) in TUNE_FIELDS.items():
+        flags |= kw[name] << shift
     load().pipck_tune(lanes_per_packet, loads_per_lane, blocks, flags)
-    load().pipck_tune_probes(1 if hdr_in_place else 0)
-    ring = (1 if ring_own_slots else 0) | (2 if ring_all_coop else 0) | {None: 0, False: 4, True: 8}[ring_adapt]
+    load().pipck_tune_probes(sum(1 << bit for name, bit in TUNE_PROBE_BITS.items() if kw[name]))
+    ring = sum(1 << bit for name, bit in TUNE_RING_BITS.items() if kw[name]) | TUNE_RING_ADAPT[ring_adapt]
     if ring or hasattr(load(), "pipck_tune_ring"):  # (a pre-1.3 build under PIPCK_LIB has no ring word)
         load().pipck_tune_ring(ring)
