@@ -61,7 +61,9 @@ uint32_t pipck_version(void);
 
 /* ---- flows / pseudo-headers ------------------------------------------ */
 /* One flow = one (src, dst, proto) pseudo-header; packet i of a batch uses
- * flow  flow_of ? flow_of[i] : (flow_origin + i) % n_flows.
+ * flow  flow_of ? flow_of[i] : (flow_origin + i) % n_flows, where
+ * flow_origin + i is taken modulo 2^64 (a u64 sum that wraps) before the
+ * remainder.
  * Addresses are in network order exactly as in struct in_addr / in6_addr.  */
 typedef struct pipck_flow4 {
     uint32_t src;      /* in_addr.s_addr */

@@ -370,9 +370,11 @@ __device__ __forceinline__ uint32_t flat_pseudo(uint64_t p0, uint32_t np, const 
     fbad = false;
     if (!pseudo || (uint32_t)lane >= np) return 0u;
     if (flow_of) return flow_pseudo(pseudo, fo, n_flows, fbad);  // n_flows bounds the entry (_n forms)
-    const uint64_t f = flow_origin + p0 + (uint64_t)lane;
-    // a 32-bit remainder where the index fits (wave-uniform test): the 64-bit one is ~100 instructions
-    return pseudo[(flow_origin + p0 + 64u) >> 32 ? (uint32_t)(f % n_flows) : (uint32_t)f % n_flows];
+    const uint64_t f0 = flow_origin + p0, f = f0 + (uint64_t)lane;  // modulo 2^64, as pipck.h states
+    // a 32-bit remainder where the task's indices f0 .. f0 + 63 all fit (wave-uniform test): the
+    // 64-bit one is ~100 instructions.  The test is on f0 itself: f0 + 64 can wrap past 2^64 and
+    // look small while f0 + lane has not.
+    return pseudo[f0 <= 0xFFFFFFFFull - 64u ? (uint32_t)f % n_flows : (uint32_t)(f % n_flows)];
 }
 
 template <bool VERIFY, bool TO_LDS = false>
@@ -1314,8 +1316,12 @@ __global__ __launch_bounds__(64) void k_packed(const uint8_t* __restrict__ arena
     uint32_t Pbase = 0;
     bool fbad = false;  // a flow_of entry past the table (n_flows bounds it in the _n forms): result 0
     if (pseudo && valid) {  // loaded now so the tile's end waits on nothing
-        const uint32_t f0 = (uint32_t)((flow_origin + tile * 64) % n_flows);  // one 64-bit modulo per tile
-        const uint32_t f = flow_of ? flow_of[seg] : (f0 + (uint32_t)lane) % n_flows;
+        const uint64_t x0 = flow_origin + tile * 64;     // modulo 2^64, as pipck.h states
+        const uint32_t f0 = (uint32_t)(x0 % n_flows);    // one 64-bit modulo per tile
+        // the lanes from 2^64 - x0 on have an index that wrapped: it is lane - (2^64 - x0), not x0 + lane
+        const uint64_t to_wrap = 0 - x0;
+        const uint32_t fl = (uint64_t)lane >= to_wrap ? (uint32_t)lane - (uint32_t)to_wrap : f0 + (uint32_t)lane;
+        const uint32_t f = flow_of ? flow_of[seg] : fl % n_flows;
         fbad = f >= n_flows;
         Pbase = fbad ? 0u : pseudo[f];
     }
@@ -1424,7 +1430,10 @@ __global__ void k_chain_finish(const uint64_t* __restrict__ seg_begin, const uin
         const uint32_t x = fseg[s];
         if (x == kBadSeg) bad = true;  // (its error bit is set already)
         total_len += x >> 16;
+        // end-around carry after every segment, as pip does (pip_checksum.cpp:110-112): F stays
+        // <= 0x1FFFE for any number of segments, and stays non-zero once it is
         F += x & 0xFFFFu;
+        F = (F & 0xFFFFu) + (F >> 16);
     }
     if (bad) {
         if (err) atomicOr(err, 1u << PIPCK_ERANGE);
@@ -1604,6 +1613,18 @@ static int launch_fixed(bool verify, const void* d_arena, uint64_t stride, uint3
     if (stride < len && n > 1) {
         set_error("pipck_checksum_fixed: stride < len");
         return PIPCK_EINVAL;
+    }
+    // Implicit flows count modulo 2^64 (pipck.h).  Several kernels step a packet's flow from an
+    // earlier packet's, which holds only while flow_origin + i does not wrap: a batch that crosses
+    // the wrap is launched as the packets before it and the packets from it on (flow_origin 0).
+    const uint64_t to_wrap = 0 - flow_origin;
+    if (d_pseudo && !d_flow_of && flow_origin && to_wrap < n) {
+        const int rc = launch_fixed(verify, d_arena, stride, len, to_wrap, d_pseudo, n_flows, d_flow_of, flow_origin,
+                                    d_out, d_ok, d_err, stream, bounded);
+        if (rc) return rc;
+        return launch_fixed(verify, (const uint8_t*)d_arena + to_wrap * stride, stride, len, n - to_wrap, d_pseudo,
+                            n_flows, d_flow_of, 0, d_out ? d_out + to_wrap : nullptr, d_ok ? d_ok + to_wrap : nullptr,
+                            d_err, stream, bounded);
     }
     if (tv.wave_arm())  // measurement arm: one packet per wave (pipck_wave.hip)
         return launch_wave(verify, false, d_arena, stride, len, nullptr, n, d_pseudo, nf, d_flow_of, flow_origin,

@@ -239,8 +239,12 @@ __device__ __forceinline__ void packedb_body(PackedbLdsT<W>& t, u32x4* hdr, cons
     uint32_t Pbase = 0;
     bool fbad = false;  // a flow_of entry past the table (n_flows bounds it in the _n forms): result 0
     if (pseudo && valid) {  // loaded now so the tile's end waits on nothing
-        const uint32_t f0 = (uint32_t)((flow_origin + tile * 64) % n_flows);
-        const uint32_t f = flow_of ? flow_of[seg] : (f0 + (uint32_t)lane) % n_flows;
+        const uint64_t x0 = flow_origin + tile * 64;  // modulo 2^64, as pipck.h states
+        const uint32_t f0 = (uint32_t)(x0 % n_flows);
+        // the lanes from 2^64 - x0 on have an index that wrapped: it is lane - (2^64 - x0), not x0 + lane
+        const uint64_t to_wrap = 0 - x0;
+        const uint32_t fl = (uint64_t)lane >= to_wrap ? (uint32_t)lane - (uint32_t)to_wrap : f0 + (uint32_t)lane;
+        const uint32_t f = flow_of ? flow_of[seg] : fl % n_flows;
         fbad = f >= n_flows;
         Pbase = fbad ? 0u : pseudo[f];
     }
