@@ -47,6 +47,14 @@ extern thread_local const void* t_last_kernel;
         hipLaunchKernelGGL(K, __VA_ARGS__);                           \
     } while (0)
 
+// The batch kernels' n_flows argument: the modulus without flow_of (never 0);
+// with it, the bound of its entries -- the caller's n_flows in the bounded _n
+// forms, UINT32_MAX (trusted) in the plain forms and for an _n call that gives
+// n_flows 0 (include/pipck.h: "n_flows 0: the entries are trusted").
+inline uint32_t kernel_n_flows(const uint32_t* d_flow_of, uint32_t n_flows, bool bounded) {
+    return d_flow_of ? (bounded && n_flows ? n_flows : UINT32_MAX) : (n_flows ? n_flows : 1u);
+}
+
 // Number of CUs on the current device (cached per device).
 int device_cus();
 

@@ -61,7 +61,7 @@ __device__ __forceinline__ void coop_body(uint32_t* s_part, const uint8_t* __res
     if (pseudo && threadIdx.x < np) {
         const uint64_t pkt = p0 + threadIdx.x;
         Pb = flow_of ? flow_pseudo(pseudo, flow_of[pkt], n_flows, fbad)
-                     : pseudo[(uint32_t)((flow_origin + pkt) % n_flows)];
+                     : pseudo[implicit_flow(flow_origin, pkt, n_flows)];
     }
     __syncthreads();
     const buf_t tb = buf_rsrc(reinterpret_cast<const u32x4*>(arena) + p0 * cpp, tchunks * 16u);
@@ -117,11 +117,11 @@ __device__ __forceinline__ void coop_body(uint32_t* s_part, const uint8_t* __res
         for (int l = 0; l < 64; l++) s += s_part[l * pitch + i];
         const uint32_t F = bswap16(fold16(s));  // packets start 16-byte aligned: even address
         const uint32_t P = pseudo ? Pb + len_term(len) : 0u;
-        if (fbad) flow_refused(err);  // a flow_of entry past the table: result 0
+        if (fbad) refuse(err);  // a flow_of entry past the table: result 0
         if (VERIFY)
-            store_result8(buf_rsrc(ok + p0, np), i, fbad ? 0u : (uint32_t)(fold16(P + F) == 0xFFFFu));
+            store_result8(buf_rsrc(ok + p0, np), i, packet_result<true, uint32_t>(P, F, fbad));
         else
-            store_result16(buf_rsrc(out + p0, 2u * np), 2u * i, fbad ? 0u : (uint32_t)finish(P, F));
+            store_result16(buf_rsrc(out + p0, 2u * np), 2u * i, packet_result<false, uint32_t>(P, F, fbad));
     }
 }
 

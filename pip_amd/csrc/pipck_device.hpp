@@ -23,6 +23,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "pipck_flow.hpp"  // fold32 / fold16 / finish, and a packet's flow, result and refusal
+
 namespace pipck {
 
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
@@ -32,9 +34,6 @@ __device__ __forceinline__ uint32_t fold64(uint64_t x) {
     return (uint32_t)(x & 0xFFFFu) + (uint32_t)((x >> 16) & 0xFFFFu) + (uint32_t)((x >> 32) & 0xFFFFu) +
            (uint32_t)(x >> 48);
 }
-__device__ __forceinline__ uint32_t fold32(uint32_t x) { return (x & 0xFFFFu) + (x >> 16); }
-// pip_fold_uint32 applied twice (pip_checksum.cpp:29-30); result in [0, 0xFFFF]
-__device__ __forceinline__ uint32_t fold16(uint32_t x) { return fold32(fold32(x)); }
 __device__ __forceinline__ uint32_t bswap16(uint32_t x) { return ((x & 0xFFu) << 8) | (x >> 8); }
 
 // Byte masks of a 16-byte chunk as two little-endian u64 halves.  The low n
@@ -89,29 +88,6 @@ __device__ __forceinline__ uint32_t be_fold(uint32_t le_residue_sum, uintptr_t s
 // pseudo-header length term: pip adds total_len hi + lo (pip_checksum.cpp:140-142);
 // identical to the flat variants' (u16)len (:91) inside the batch domain.
 __device__ __forceinline__ uint32_t len_term(uint32_t len) { return (len >> 16) + (len & 0xFFFFu); }
-
-// ~(u16)fold(fold(P + F)) -- the two folds of pip_standard_checksum
-// (pip_checksum.cpp:29-30) and the final ~ of pip_inet_checksum (:60),
-// pip_inet6_checksum (:86), pip_inet_checksum_buf (:114), pip_inet6_checksum_buf (:147)
-__device__ __forceinline__ uint16_t finish(uint32_t pseudo_total, uint32_t be_sum) {
-    return (uint16_t)~fold16(pseudo_total + be_sum);
-}
-
-// Pseudo-header base of a packet whose flow comes from a flow_of entry f.  The
-// fixed-stride kernels get nf = the table's entries in the bounded _n forms
-// (UINT32_MAX in the plain ones: trusted).  pip has no flow index to go stale --
-// it passes the addresses by value on every call (pip_checksum.cpp:42,63) -- so
-// an entry past the table is this engine's own failure mode and must never
-// become a read outside the table: `bad` is set, the table is not read, and the
-// caller stores 0 for that packet and reports it with flow_refused().
-__device__ __forceinline__ uint32_t flow_pseudo(const uint32_t* pseudo, uint32_t f, uint32_t nf, bool& bad) {
-    bad = f >= nf;
-    return bad ? 0u : pseudo[f];
-}
-constexpr uint32_t kErrRange = 1u << 2;  // 1 << PIPCK_ERANGE (include/pipck.h)
-__device__ __forceinline__ void flow_refused(uint32_t* err) {
-    if (err) atomicOr(err, kErrRange);
-}
 
 // Arena loads are issued in the global address space explicitly.  A pointer
 // rebuilt from an integer (the ragged kernel's LDS segment bases) is otherwise

@@ -116,7 +116,7 @@ __global__ __launch_bounds__(256) void k_hdr(const uint8_t* __restrict__ arena, 
                 const uint32_t hi = r * PR + (uint32_t)fin;
                 if (fin >= 0 && hi < np) {
                     const uint32_t F = bswap16(fold16(Tp + H));
-                    res[hi] = VERIFY ? (uint16_t)(fold16(F) == 0xFFFFu) : (uint16_t)(~F & 0xFFFFu);
+                    res[hi] = (uint16_t)packet_result<VERIFY>(0u, F, false);  // no pseudo-header: P == 0
                 }
             }
             // the row U ahead (unconditional: past the task it reads zeros, no request)

@@ -45,7 +45,7 @@
 
 namespace pipck {
 
-static_assert(kErrRange == 1u << PIPCK_ERANGE, "pipck_device.hpp's error bit must match include/pipck.h");
+static_assert(kErrRange == 1u << PIPCK_ERANGE, "pipck_flow.hpp's error bit must match include/pipck.h");
 
 // ---------------------------------------------------------------------------
 // flows -> pseudo-header bases
@@ -86,12 +86,8 @@ __global__ __launch_bounds__(256) void k_fixed(const uint8_t* __restrict__ arena
     uint64_t pkt = (uint64_t)blockIdx.x * GPB + threadIdx.x / G;
     const uint64_t step = (uint64_t)gridDim.x * GPB;
     const uint32_t lterm = len_term(len);
-    const bool implicit_flow = pseudo != nullptr && flow_of == nullptr;
-    uint32_t flow = 0, flow_step = 0;
-    if (implicit_flow) {  // one 64-bit modulo per thread, then incremental
-        flow = (uint32_t)((flow_origin + pkt) % n_flows);
-        flow_step = (uint32_t)(step % n_flows);
-    }
+    const bool implicit = pseudo != nullptr && flow_of == nullptr;
+    FlowWalk fw(implicit, flow_origin, pkt, step, n_flows);  // one 64-bit modulo per thread, then incremental
     for (; pkt < n; pkt += step) {
         const uintptr_t addr = (uintptr_t)arena + pkt * stride;
         const int head = (int)(addr & 15);
@@ -124,17 +120,14 @@ __global__ __launch_bounds__(256) void k_fixed(const uint8_t* __restrict__ arena
             const uint32_t F = be_fold(s, addr);
             uint32_t P = 0;
             bool fbad = false;  // a flow_of entry past the table (_n forms): result 0, ERANGE
-            if (pseudo) P = (flow_of ? flow_pseudo(pseudo, flow_of[pkt], n_flows, fbad) : pseudo[flow]) + lterm;
+            if (pseudo) P = (flow_of ? flow_pseudo(pseudo, flow_of[pkt], n_flows, fbad) : pseudo[fw.flow]) + lterm;
             if (VERIFY)
-                ok[pkt] = !fbad && fold16(P + F) == 0xFFFFu;
+                ok[pkt] = packet_result<true>(P, F, fbad);
             else
-                out[pkt] = fbad ? (uint16_t)0 : finish(P, F);
-            if (fbad) flow_refused(err);
+                out[pkt] = packet_result<false>(P, F, fbad);
+            if (fbad) refuse(err);
         }
-        if (implicit_flow) {
-            flow += flow_step;
-            if (flow >= n_flows) flow -= n_flows;
-        }
+        if (implicit) fw.next();
     }
 }
 
@@ -162,6 +155,9 @@ __global__ __launch_bounds__(256) void k_small(const uint8_t* __restrict__ arena
     u32x4 v[K][NL];
     uint32_t P[K];
     uint32_t fbad = 0;  // bit k: packet k's flow_of entry is past the table (_n forms): result 0, ERANGE
+    // FlowWalk's walk (pipck_flow.hpp: start base + lane, step 64, same precondition), spelled out:
+    // through the struct the start's modulo and the step's reduction come out in another order
+    // and every instantiation's code changes.
     uint32_t flow = 0;
     if (pseudo && !flow_of) flow = (uint32_t)((flow_origin + base + lane) % n_flows);
     const uint32_t fstep = pseudo && !flow_of ? 64u % n_flows : 0u;
@@ -205,10 +201,12 @@ __global__ __launch_bounds__(256) void k_small(const uint8_t* __restrict__ arena
             acc += sum4(x);
         }
         const uint32_t F = be_fold(fold64(acc), addr);
-        res[k] = VERIFY ? (uint32_t)(fold16(P[k] + lterm + F) == 0xFFFFu) : (uint32_t)finish(P[k] + lterm, F);
+        // computed for every packet, then forced to 0 (as packet_result does when told of `bad`,
+        // which here costs other registers in all 64 instantiations)
+        res[k] = packet_result<VERIFY>(P[k] + lterm, F, false);
         if ((fbad >> k) & 1u) res[k] = 0;
     }
-    if (fbad) flow_refused(err);
+    if (fbad) refuse(err);
     // Non-temporal result stores.  Results are 2 B per 20-B header here (10 %
     // of the bytes, unlike the streaming kernels' 0.1 %): the write-through sc1
     // policy that the streaming kernels use measured 0.5-1 % slower at 64M-256M
@@ -370,11 +368,7 @@ __device__ __forceinline__ uint32_t flat_pseudo(uint64_t p0, uint32_t np, const 
     fbad = false;
     if (!pseudo || (uint32_t)lane >= np) return 0u;
     if (flow_of) return flow_pseudo(pseudo, fo, n_flows, fbad);  // n_flows bounds the entry (_n forms)
-    const uint64_t f0 = flow_origin + p0, f = f0 + (uint64_t)lane;  // modulo 2^64, as pipck.h states
-    // a 32-bit remainder where the task's indices f0 .. f0 + 63 all fit (wave-uniform test): the
-    // 64-bit one is ~100 instructions.  The test is on f0 itself: f0 + 64 can wrap past 2^64 and
-    // look small while f0 + lane has not.
-    return pseudo[f0 <= 0xFFFFFFFFull - 64u ? (uint32_t)f % n_flows : (uint32_t)(f % n_flows)];
+    return pseudo[task_flow(flow_origin, p0, (uint32_t)lane, n_flows)];
 }
 
 template <bool VERIFY, bool TO_LDS = false>
@@ -388,10 +382,12 @@ __device__ __forceinline__ void flat_write(const uint16_t* part, uint32_t pitch,
     const uint32_t F = bswap16(fold16(s));  // packets start 16-byte aligned: even address
     const uint32_t P = has_pseudo ? Pb + lterm : 0u;
     const uint64_t pkt = p0 + lane;
-    uint32_t r = VERIFY ? (uint32_t)(fold16(P + F) == 0xFFFFu) : (uint32_t)finish(P, F);
+    // packet_result(P, F, fbad, err) written out: through it the checksum's `~` compiles to
+    // another immediate in every k_flat
+    uint32_t r = packet_result<VERIFY>(P, F, false);
     if (fbad) {  // a flow_of entry past the table: result 0, ERANGE
         r = 0;
-        flow_refused(err);
+        refuse(err);
     }
     if (!TO_LDS && (kflags & kEndNoStore) && (uint64_t)r != magic) return;  // measurement: never stores
     if (TO_LDS) {
@@ -749,6 +745,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(flat_waves_
             }
         }
         wave_sync();
+        // FlowWalk's walk (start p0 + lane, step 64, same precondition), spelled out as in k_small
         uint32_t flow = 0;
         const uint32_t fstep = pseudo && !flow_of ? 64u % n_flows : 0u;
         if (pseudo && !flow_of) flow = (uint32_t)((flow_origin + p0 + lane) % n_flows);
@@ -759,10 +756,10 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(flat_waves_
             bool fbad = false;  // a flow_of entry past the table (_n forms): result 0, ERANGE
             if (pseudo) P = (flow_of ? flow_pseudo(pseudo, flow_of[pkt], n_flows, fbad) : pseudo[flow]) + lterm;
             if (VERIFY)
-                ok[pkt] = !fbad && fold16(P + F) == 0xFFFFu;
+                ok[pkt] = packet_result<true>(P, F, fbad);
             else
-                out[pkt] = fbad ? (uint16_t)0 : finish(P, F);
-            if (fbad) flow_refused(err);
+                out[pkt] = packet_result<false>(P, F, fbad);
+            if (fbad) refuse(err);
             flow += fstep;
             if (flow >= n_flows) flow -= n_flows;
         }
@@ -875,14 +872,13 @@ __global__ __launch_bounds__(256) void k_flat_tiny(const uint8_t* __restrict__ a
             uint32_t P_ = 0;
             bool fbad = false;  // a flow_of entry past the table (_n forms): result 0, ERANGE
             if (pseudo) P_ = (flow_of ? flow_pseudo(pseudo, flow_of[p0 + i], n_flows, fbad) : pseudo[flow]) + lterm;
-            if (fbad) {
-                flow_refused(err);
-                return 0u;
-            }
-            return VERIFY ? (uint32_t)(fold16(P_ + F) == 0xFFFFu) : (uint32_t)finish(P_, F);
+            if (fbad) refuse(err);
+            return packet_result<VERIFY, uint32_t>(P_, F, fbad);
         };
         const bool vec = ((VERIFY ? (uintptr_t)ok : (uintptr_t)out) & (VERIFY ? 3u : 7u)) == 0;  // p0 % 64 == 0
         const uint32_t nvec = vec ? np & ~3u : 0u;
+        // FlowWalk's walk three times (steps 256, 1 inside a group of four, 64; same
+        // precondition), spelled out as in k_small
         uint32_t flow = 0;
         const uint32_t fstep4 = pseudo && !flow_of ? 256u % n_flows : 0u;
         if (pseudo && !flow_of) flow = (uint32_t)((flow_origin + p0 + 4u * lane) % n_flows);
@@ -1275,15 +1271,15 @@ __global__ __launch_bounds__(256) void k_ragged(const uint8_t* __restrict__ aren
             if (FINAL) {
                 const uint32_t P = pseudo ? Pbase + len_term(len) : 0u;
                 if (ok)  // RX verification: valid iff the sum incl. the checksum field folds to 0xFFFF
-                    ok[seg] = !bad && fold16(P + F) == 0xFFFFu;
+                    ok[seg] = packet_result<true>(P, F, bad);
                 else
-                    out[seg] = bad ? (uint16_t)0 : finish(P, F);
+                    out[seg] = packet_result<false>(P, F, bad);
             } else {
                 // len <= 65535; a bad segment gets kBadSeg (length 0 with a nonzero
                 // sum: no real segment) so k_chain_finish zeroes its packet
                 fseg[seg] = bad ? kBadSeg : (len << 16) | F;
             }
-            if (bad && err) atomicOr(err, 1u << PIPCK_ERANGE);
+            refuse(err, bad);
         }
         wave_sync();
     }
@@ -1316,14 +1312,9 @@ __global__ __launch_bounds__(64) void k_packed(const uint8_t* __restrict__ arena
     uint32_t Pbase = 0;
     bool fbad = false;  // a flow_of entry past the table (n_flows bounds it in the _n forms): result 0
     if (pseudo && valid) {  // loaded now so the tile's end waits on nothing
-        const uint64_t x0 = flow_origin + tile * 64;     // modulo 2^64, as pipck.h states
-        const uint32_t f0 = (uint32_t)(x0 % n_flows);    // one 64-bit modulo per tile
-        // the lanes from 2^64 - x0 on have an index that wrapped: it is lane - (2^64 - x0), not x0 + lane
-        const uint64_t to_wrap = 0 - x0;
-        const uint32_t fl = (uint64_t)lane >= to_wrap ? (uint32_t)lane - (uint32_t)to_wrap : f0 + (uint32_t)lane;
-        const uint32_t f = flow_of ? flow_of[seg] : fl % n_flows;
-        fbad = f >= n_flows;
-        Pbase = fbad ? 0u : pseudo[f];
+        const TileFlow tf(flow_origin, tile, (uint32_t)lane, n_flows);  // one 64-bit modulo per tile
+        const uint32_t f = flow_of ? flow_of[seg] : tf.flow();
+        Pbase = flow_pseudo(pseudo, f, n_flows, fbad);
     }
     // The tile's row grid starts on the 128-B line holding its first byte: the
     // `lead` chunks before it (the previous tile's last bytes) are loaded and
@@ -1339,7 +1330,7 @@ __global__ __launch_bounds__(64) void k_packed(const uint8_t* __restrict__ arena
     const uint64_t tc0 = tile_chunk[tile];
     const uint32_t tile_ch = (uint32_t)__builtin_amdgcn_readlane((int)wave_incl_scan(nch), 63);
     if (!(tc0 <= arena_chunks && (uint64_t)tile_ch <= arena_chunks - tc0)) {
-        if (lane == 0 && err) atomicOr(err, 1u << PIPCK_ERANGE);
+        refuse(err, lane == 0);
         if (VERIFY)
             store_result8(buf_rsrc(ok + tile * 64, nv), (uint32_t)lane, 0u);
         else
@@ -1356,11 +1347,7 @@ __global__ __launch_bounds__(64) void k_packed(const uint8_t* __restrict__ arena
                                                          true, MARKS ? kflags | kPackedMarksOnly : kflags, lead);
     const uint32_t F = bswap16(fold16(le_sum));  // 16-byte aligned: even address
     const uint32_t P = pseudo ? Pbase + len : 0u;
-    uint32_t r = VERIFY ? (uint32_t)(fold16(P + F) == 0xFFFFu) : (uint32_t)finish(P, F);
-    if (fbad) {
-        r = 0;
-        if (err) atomicOr(err, 1u << PIPCK_ERANGE);
-    }
+    const uint32_t r = packet_result<VERIFY>(P, F, fbad, err);
     if (kflags & kPlainResultStores) {
         if (valid) {
             if (VERIFY)
@@ -1374,41 +1361,6 @@ __global__ __launch_bounds__(64) void k_packed(const uint8_t* __restrict__ arena
         store_result16(buf_rsrc(out + tile * 64, 2u * nv), 2u * (uint32_t)lane, r);
     }
     trace_task(kflags, trb, tile, t_start, lane);
-}
-
-// Index of a packed batch: tile_chunk[t] for t = 0 .. ceil(n/64) (the last
-// entry = the arena's chunks).  Pass 1 sums each tile's chunks into
-// tile_chunk[t + 1]; pass 2, one block, turns them into a prefix in place.
-__global__ __launch_bounds__(64) void k_packed_tile_sums(const uint16_t* __restrict__ lens, uint64_t n,
-                                                         uint64_t* __restrict__ tile_chunk) {
-    const uint64_t seg = (uint64_t)blockIdx.x * 64 + threadIdx.x;
-    const uint32_t nch = seg < n ? (lens[seg] + 15u) >> 4 : 0u;
-    const uint32_t tot = (uint32_t)__builtin_amdgcn_readlane((int)wave_incl_scan(nch), 63);
-    if (threadIdx.x == 0) tile_chunk[blockIdx.x + 1] = tot;
-}
-
-__global__ __launch_bounds__(1024) void k_packed_tile_scan(uint64_t* __restrict__ tile_chunk, uint64_t n_tiles) {
-    __shared__ uint64_t part[1024];
-    const uint32_t i = threadIdx.x;
-    const uint64_t per = (n_tiles + 1023) / 1024, b = min<uint64_t>(n_tiles, i * per), e = min<uint64_t>(n_tiles, b + per);
-    uint64_t s = 0;
-    for (uint64_t k = b; k < e; k++) s += tile_chunk[k + 1];
-    part[i] = s;
-    __syncthreads();
-    for (uint32_t off = 1; off < 1024; off <<= 1) {  // Hillis-Steele inclusive scan of the 1024 partials
-        const uint64_t x = i >= off ? part[i - off] : 0ull;
-        __syncthreads();
-        part[i] += x;
-        __syncthreads();
-    }
-    // entries k+1 of this thread's range become inclusive prefixes (= the
-    // exclusive prefix of tile k+1); each thread touches only its own entries
-    uint64_t run = part[i] - s;
-    for (uint64_t k = b; k < e; k++) {
-        run += tile_chunk[k + 1];
-        tile_chunk[k + 1] = run;
-    }
-    if (i == 0) tile_chunk[0] = 0;
 }
 
 // Per packet: the segments' folded sums and lengths, packed by k_ragged as
@@ -1436,7 +1388,7 @@ __global__ void k_chain_finish(const uint64_t* __restrict__ seg_begin, const uin
         F = (F & 0xFFFFu) + (F >> 16);
     }
     if (bad) {
-        if (err) atomicOr(err, 1u << PIPCK_ERANGE);
+        refuse(err);
         out[p] = 0;
         return;
     }
@@ -1608,8 +1560,7 @@ static int launch_fixed(bool verify, const void* d_arena, uint64_t stride, uint3
         set_error("pipck_checksum_fixed: n_flows == 0");
         return PIPCK_EINVAL;
     }
-    // the kernels' n_flows: the modulus without flow_of; with it, the bound of its entries
-    const uint32_t nf = d_flow_of ? (bounded ? n_flows : UINT32_MAX) : (n_flows ? n_flows : 1u);
+    const uint32_t nf = kernel_n_flows(d_flow_of, n_flows, bounded);
     if (stride < len && n > 1) {
         set_error("pipck_checksum_fixed: stride < len");
         return PIPCK_EINVAL;
@@ -1851,8 +1802,7 @@ static int launch_packed(bool verify, const void* d_arena, uint64_t arena_bytes,
     // packets, 2.448 vs 2.518 ms against the ring of 24 with the end loop, each
     // alone gaining less (profiles/r02_knob_scan_cfg4_packed.jsonl).
     const uint32_t f = tv.flags ^ kPackedMarksOnly;
-    // the kernel's n_flows: the modulus without flow_of; with it, the bound of its entries
-    const uint32_t nf = d_flow_of ? (bounded && n_flows ? n_flows : UINT32_MAX) : (n_flows ? n_flows : 1u);
+    const uint32_t nf = kernel_n_flows(d_flow_of, n_flows, bounded);
     // rows in flight per wave: loads_per_lane 17/25 = rings of 16/24, anything else 32
     const int ui = tv.loads == 17 ? 0 : (tv.loads == 25 ? 1 : 2);
     PIPCK_LAUNCH(kPacked[ui][!verify][!tv.nt(true)][!(f & kPackedMarksOnly)], dim3((uint32_t)tiles), dim3(64), 0, s,
@@ -2076,26 +2026,6 @@ int pipck_verify_packed(const void* d_arena, const uint16_t* d_lens, const uint6
                         uint8_t* d_ok, void* stream) {
     return launch_packed(true, d_arena, UINT64_MAX, d_lens, d_tile_chunk, n, d_pseudo, n_flows, d_flow_of,
                          flow_origin, nullptr, d_ok, nullptr, as_stream(stream), false);
-}
-
-int pipck_packed_index(const uint16_t* d_lens, uint64_t n, uint64_t* d_tile_chunk, void* stream) {
-    if (!d_tile_chunk || (n && !d_lens)) {
-        set_error("pipck_packed_index: null pointer");
-        return PIPCK_EINVAL;
-    }
-    const uint64_t tiles = (n + 63) / 64;
-    if (tiles > 0x7FFFFFFFull) {
-        set_error("pipck_packed_index: more than 2^37 packets");
-        return PIPCK_ERANGE;
-    }
-    hipStream_t s = as_stream(stream);
-    if (tiles) {
-        hipLaunchKernelGGL(k_packed_tile_sums, dim3((uint32_t)tiles), dim3(64), 0, s, d_lens, n, d_tile_chunk);
-        PIPCK_LAUNCHED("k_packed_tile_sums");
-    }
-    hipLaunchKernelGGL(k_packed_tile_scan, dim3(1), dim3(1024), 0, s, d_tile_chunk, tiles);
-    PIPCK_LAUNCHED("k_packed_tile_scan");
-    return PIPCK_OK;
 }
 
 int pipck_checksum_chains_n(const void* d_arena, uint64_t arena_bytes, const pipck_desc* d_segs, uint64_t n_segs,

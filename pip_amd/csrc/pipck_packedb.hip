@@ -239,14 +239,9 @@ __device__ __forceinline__ void packedb_body(PackedbLdsT<W>& t, u32x4* hdr, cons
     uint32_t Pbase = 0;
     bool fbad = false;  // a flow_of entry past the table (n_flows bounds it in the _n forms): result 0
     if (pseudo && valid) {  // loaded now so the tile's end waits on nothing
-        const uint64_t x0 = flow_origin + tile * 64;  // modulo 2^64, as pipck.h states
-        const uint32_t f0 = (uint32_t)(x0 % n_flows);
-        // the lanes from 2^64 - x0 on have an index that wrapped: it is lane - (2^64 - x0), not x0 + lane
-        const uint64_t to_wrap = 0 - x0;
-        const uint32_t fl = (uint64_t)lane >= to_wrap ? (uint32_t)lane - (uint32_t)to_wrap : f0 + (uint32_t)lane;
-        const uint32_t f = flow_of ? flow_of[seg] : fl % n_flows;
-        fbad = f >= n_flows;
-        Pbase = fbad ? 0u : pseudo[f];
+        const TileFlow tf(flow_origin, tile, (uint32_t)lane, n_flows);  // one 64-bit modulo per tile
+        const uint32_t f = flow_of ? flow_of[seg] : tf.flow();
+        Pbase = flow_pseudo(pseudo, f, n_flows, fbad);
     }
     const uint32_t nv = (uint32_t)min<uint64_t>(64, n - tile * 64);
     const uint32_t incl = wave_incl_scan(len);
@@ -259,7 +254,7 @@ __device__ __forceinline__ void packedb_body(PackedbLdsT<W>& t, u32x4* hdr, cons
     const bool in_arena = toff <= arena_bytes && (uint64_t)tile_len <= arena_bytes - toff;
     if (!in_arena) {  // (block-uniform: every wave read the same index)
         if (w != 0) return;
-        if (lane == 0 && err) atomicOr(err, 1u << PIPCK_ERANGE);
+        refuse(err, lane == 0);
         if (VERIFY)
             store_result8(buf_rsrc(ok + tile * 64, nv), (uint32_t)lane, 0u);
         else
@@ -335,11 +330,7 @@ __device__ __forceinline__ void packedb_body(PackedbLdsT<W>& t, u32x4* hdr, cons
             r = valid ? rx_from_window(pk, len, F, hw) : 0u;
         }
     } else {
-        r = VERIFY ? (uint32_t)(fold16(P + F) == 0xFFFFu) : (uint32_t)finish(P, F);
-        if (fbad) {
-            r = 0;
-            if (err) atomicOr(err, 1u << PIPCK_ERANGE);
-        }
+        r = packet_result<VERIFY>(P, F, fbad, err);
     }
     if (VERIFY)  // write-through result stores (store_result16); lanes past the batch are range-checked off
         store_result8(buf_rsrc(ok + tile * 64, nv), (uint32_t)lane, r);
@@ -413,22 +404,25 @@ static int packedb_shape(bool rx, const TuneView& tv) {
     }
 }
 
-// tile_off[t] = bytes of every packet before packet 64 t (the last entry = the
-// batch's bytes): pass 1 sums each tile's lengths into tile_off[t + 1], pass 2
-// (one block) turns them into a prefix in place.
-__global__ __launch_bounds__(64) void k_packedb_tile_sums(const uint16_t* __restrict__ lens, uint64_t n,
-                                                          uint64_t* __restrict__ tile_off) {
+// The index of a packed batch: index[t] = the units of every packet before packet
+// 64 t, t = 0 .. ceil(n/64) (the last entry = the batch's units).  Units: bytes
+// (tile_off), or with CHUNKS lengths rounded up to 16-byte chunks (k_packed's
+// tile_chunk).  Pass 1 sums each tile into index[t + 1]; pass 2 (one block) scans.
+template <bool CHUNKS>
+__global__ __launch_bounds__(64) void k_tile_sums(const uint16_t* __restrict__ lens, uint64_t n,
+                                                  uint64_t* __restrict__ index) {
     const uint64_t seg = (uint64_t)blockIdx.x * 64 + threadIdx.x;
-    const uint32_t tot = wave_total(seg < n ? lens[seg] : 0u);
-    if (threadIdx.x == 0) tile_off[blockIdx.x + 1] = tot;
+    const uint32_t len = seg < n ? lens[seg] : 0u;
+    const uint32_t tot = wave_total(CHUNKS ? (len + 15u) >> 4 : len);
+    if (threadIdx.x == 0) index[blockIdx.x + 1] = tot;
 }
 
-__global__ __launch_bounds__(1024) void k_packedb_tile_scan(uint64_t* __restrict__ tile_off, uint64_t n_tiles) {
+__global__ __launch_bounds__(1024) void k_tile_scan(uint64_t* __restrict__ index, uint64_t n_tiles) {
     __shared__ uint64_t part[1024];
     const uint32_t i = threadIdx.x;
     const uint64_t per = (n_tiles + 1023) / 1024, b = min<uint64_t>(n_tiles, i * per), e = min<uint64_t>(n_tiles, b + per);
     uint64_t s = 0;
-    for (uint64_t k = b; k < e; k++) s += tile_off[k + 1];
+    for (uint64_t k = b; k < e; k++) s += index[k + 1];
     part[i] = s;
     __syncthreads();
     for (uint32_t off = 1; off < 1024; off <<= 1) {  // Hillis-Steele inclusive scan of the 1024 partials
@@ -437,12 +431,45 @@ __global__ __launch_bounds__(1024) void k_packedb_tile_scan(uint64_t* __restrict
         part[i] += x;
         __syncthreads();
     }
+    // entries k+1 of this thread's range become inclusive prefixes (= the
+    // exclusive prefix of tile k+1); each thread touches only its own entries
     uint64_t run = part[i] - s;
     for (uint64_t k = b; k < e; k++) {
-        run += tile_off[k + 1];
-        tile_off[k + 1] = run;
+        run += index[k + 1];
+        index[k + 1] = run;
     }
-    if (i == 0) tile_off[0] = 0;
+    if (i == 0) index[0] = 0;
+}
+
+static int arg_error(int rc, const char* entry, const char* what) {  // `entry`: the C function the message names
+    set_error(std::string(entry) + what);
+    return rc;
+}
+
+template <bool CHUNKS>
+static int build_tile_index(const char* entry, const uint16_t* d_lens, uint64_t n, uint64_t* d_index, void* stream) {
+    if (!d_index || (n && !d_lens)) return arg_error(PIPCK_EINVAL, entry, ": null pointer");
+    const uint64_t tiles = (n + 63) / 64;
+    if (tiles > 0x7FFFFFFFull) return arg_error(PIPCK_ERANGE, entry, ": more than 2^37 packets");
+    hipStream_t s = as_stream(stream);
+    if (tiles) {
+        hipLaunchKernelGGL(k_tile_sums<CHUNKS>, dim3((uint32_t)tiles), dim3(64), 0, s, d_lens, n, d_index);
+        PIPCK_LAUNCHED("k_tile_sums");
+    }
+    hipLaunchKernelGGL(k_tile_scan, dim3(1), dim3(1024), 0, s, d_index, tiles);
+    PIPCK_LAUNCHED("k_tile_scan");
+    return PIPCK_OK;
+}
+
+// The argument checks the three byte-packed launches share; the tile count in *tiles.
+static int packedb_check(const char* entry, const void* d_arena, const uint16_t* d_lens, const uint64_t* d_tile_off,
+                         const void* d_result, uint64_t n, bool no_modulus, uint64_t* tiles) {
+    if (!d_arena || !d_lens || !d_tile_off || !d_result) return arg_error(PIPCK_EINVAL, entry, ": null pointer");
+    if ((uintptr_t)d_arena % 128) return arg_error(PIPCK_EINVAL, entry, ": the arena must be 128-byte aligned");
+    if (no_modulus) return arg_error(PIPCK_EINVAL, entry, ": n_flows == 0");  // implicit flows, n_flows == 0
+    *tiles = (n + 63) / 64;
+    if (*tiles > 0x7FFFFFFFull) return arg_error(PIPCK_ERANGE, entry, ": more than 2^37 packets in one launch");
+    return PIPCK_OK;
 }
 
 // bounded: the _n forms (flow_of entries bounded by n_flows when it is given)
@@ -451,25 +478,12 @@ static int launch_packedb(bool verify, const void* d_arena, uint64_t arena_bytes
                           const uint32_t* d_flow_of, uint64_t flow_origin, uint16_t* d_out, uint8_t* d_ok,
                           uint32_t* d_err, hipStream_t s, bool bounded = true) {
     if (n == 0) return PIPCK_OK;
-    if (!d_arena || !d_lens || !d_tile_off || (verify ? !d_ok : !d_out)) {
-        set_error("pipck_checksum_packed_bytes: null pointer");
-        return PIPCK_EINVAL;
-    }
-    if ((uintptr_t)d_arena % 128) {
-        set_error("pipck_checksum_packed_bytes: the arena must be 128-byte aligned");
-        return PIPCK_EINVAL;
-    }
-    if (d_pseudo && !d_flow_of && n_flows == 0) {
-        set_error("pipck_checksum_packed_bytes: n_flows == 0");
-        return PIPCK_EINVAL;
-    }
-    const uint64_t tiles = (n + 63) / 64;
-    if (tiles > 0x7FFFFFFFull) {
-        set_error("pipck_checksum_packed_bytes: more than 2^37 packets in one launch");
-        return PIPCK_ERANGE;
-    }
-    // the kernel's n_flows: the modulus without flow_of; with it, the bound of its entries
-    const uint32_t nf = d_flow_of ? (bounded && n_flows ? n_flows : UINT32_MAX) : (n_flows ? n_flows : 1u);
+    uint64_t tiles;
+    if (const int rc = packedb_check("pipck_checksum_packed_bytes", d_arena, d_lens, d_tile_off,
+                                     verify ? (const void*)d_ok : (const void*)d_out, n,
+                                     d_pseudo && !d_flow_of && n_flows == 0, &tiles))
+        return rc;
+    const uint32_t nf = kernel_n_flows(d_flow_of, n_flows, bounded);
     const uint8_t* a = (const uint8_t*)d_arena;
 #define PIPCK_PB(WW, UU)                                                                                       \
     case WW * 100 + UU:                                                                                        \
@@ -499,19 +513,9 @@ static int launch_packedb(bool verify, const void* d_arena, uint64_t arena_bytes
 int launch_packedb_rx(const void* d_arena, uint64_t arena_bytes, const uint16_t* d_lens, const uint64_t* d_tile_off,
                       uint64_t n, uint8_t* d_ok, uint32_t* d_err, hipStream_t s) {
     if (n == 0) return PIPCK_OK;
-    if (!d_arena || !d_lens || !d_tile_off || !d_ok) {
-        set_error("pipck_rx_verify_device: null pointer");
-        return PIPCK_EINVAL;
-    }
-    if ((uintptr_t)d_arena % 128) {
-        set_error("pipck_rx_verify_device: the arena must be 128-byte aligned");
-        return PIPCK_EINVAL;
-    }
-    const uint64_t tiles = (n + 63) / 64;
-    if (tiles > 0x7FFFFFFFull) {
-        set_error("pipck_rx_verify_device: more than 2^37 packets in one launch");
-        return PIPCK_ERANGE;
-    }
+    uint64_t tiles;
+    if (const int rc = packedb_check("pipck_rx_verify_device", d_arena, d_lens, d_tile_off, d_ok, n, false, &tiles))
+        return rc;
     const uint8_t* a = (const uint8_t*)d_arena;
 #define PIPCK_PBRX(WW, UU)                                                                                     \
     case WW * 100 + UU:                                                                                        \
@@ -539,19 +543,9 @@ int launch_packedb_tx(void* d_arena, uint64_t arena_bytes, const uint16_t* d_len
         return PIPCK_EINVAL;
     }
     if (n == 0) return PIPCK_OK;
-    if (!d_arena || !d_lens || !d_tile_off || !d_done) {
-        set_error("pipck_tx_fill_device: null pointer");
-        return PIPCK_EINVAL;
-    }
-    if ((uintptr_t)d_arena % 128) {
-        set_error("pipck_tx_fill_device: the arena must be 128-byte aligned");
-        return PIPCK_EINVAL;
-    }
-    const uint64_t tiles = (n + 63) / 64;
-    if (tiles > 0x7FFFFFFFull) {
-        set_error("pipck_tx_fill_device: more than 2^37 packets in one launch");
-        return PIPCK_ERANGE;
-    }
+    uint64_t tiles;
+    if (const int rc = packedb_check("pipck_tx_fill_device", d_arena, d_lens, d_tile_off, d_done, n, false, &tiles))
+        return rc;
     uint8_t* a = (uint8_t*)d_arena;
 #define PIPCK_PBTX(WW, UU)                                                                                     \
     case WW * 100 + UU:                                                                                        \
@@ -612,23 +606,12 @@ int pipck_tx_fill_device(void* d_arena, uint64_t arena_bytes, const uint16_t* d_
 }
 
 int pipck_packed_bytes_index(const uint16_t* d_lens, uint64_t n, uint64_t* d_tile_off, void* stream) {
-    if (!d_tile_off || (n && !d_lens)) {
-        set_error("pipck_packed_bytes_index: null pointer");
-        return PIPCK_EINVAL;
-    }
-    const uint64_t tiles = (n + 63) / 64;
-    if (tiles > 0x7FFFFFFFull) {
-        set_error("pipck_packed_bytes_index: more than 2^37 packets");
-        return PIPCK_ERANGE;
-    }
-    hipStream_t s = as_stream(stream);
-    if (tiles) {
-        hipLaunchKernelGGL(k_packedb_tile_sums, dim3((uint32_t)tiles), dim3(64), 0, s, d_lens, n, d_tile_off);
-        PIPCK_LAUNCHED("k_packedb_tile_sums");
-    }
-    hipLaunchKernelGGL(k_packedb_tile_scan, dim3(1), dim3(1024), 0, s, d_tile_off, tiles);
-    PIPCK_LAUNCHED("k_packedb_tile_scan");
-    return PIPCK_OK;
+    return build_tile_index<false>("pipck_packed_bytes_index", d_lens, n, d_tile_off, stream);
+}
+
+// the 16-byte layout's index (k_packed, pipck_kernels.hip): chunks instead of bytes
+int pipck_packed_index(const uint16_t* d_lens, uint64_t n, uint64_t* d_tile_chunk, void* stream) {
+    return build_tile_index<true>("pipck_packed_index", d_lens, n, d_tile_chunk, stream);
 }
 
 }  // extern "C"

@@ -210,7 +210,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void k
         }
         const uint8_t* pkp = arena + (p0 + i) * cpp * 16u;
         const bool bad = (uint32_t)lens[p0 + i] > 16u * cpp;
-        if (bad && err) atomicOr(err, 1u << PIPCK_ERANGE);
+        if (bad && err) refuse(err);  // (refuse's own null test, kept in this condition: the loop's code depends on it)
         store_result8(buf_rsrc(ok + p0, np), i, bad ? 0u : rx_from_window(pkp, L, F, hw));
     }
     // the feedback (launch_ring_rx passes it for jumbo slots only, where K <= 64)
@@ -289,7 +289,7 @@ __global__ __launch_bounds__(256) void k_ring_slots(const uint8_t* __restrict__ 
         }
         const uint8_t* pkp = arena + (b0 + i) * cpp * 16u;
         const bool bad = Li > 16u * cpp;
-        if (bad && err) atomicOr(err, 1u << PIPCK_ERANGE);
+        if (bad && err) refuse(err);  // (as in k_ring_rx)
         store_result8(buf_rsrc(ok + b0, np), i, bad ? 0u : rx_from_window(pkp, Li, F, hw));
     }
 }
@@ -497,7 +497,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_num_sgpr(80))) void k_ri
         }
         r = rx_from_window(arena + (b0 + (uint32_t)lane) * stride, L, F, hw);
     }
-    if (bad && err) atomicOr(err, 1u << PIPCK_ERANGE);
+    refuse(err, bad);
     store_result8(buf_rsrc(ok + b0, nb), (uint32_t)lane, r);
     if (fb.ctr && blockIdx.x % fb.every == 0)  // the schedule's feedback (wave 0, after its stores)
         ring_report(fb, ring_dense(wave_total((nch + 63u) >> 6), nb, stride), lane);

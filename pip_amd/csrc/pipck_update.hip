@@ -48,14 +48,14 @@ __global__ __launch_bounds__(256) void k_update_fixed(uint8_t* __restrict__ aren
     const uint8_t* e = nb + i * new_stride;
     uint32_t po = 0, pn = 0;
     if (pseudo_old) {
-        const uint32_t f = flow_of ? flow_of[i] : (uint32_t)((flow_origin + i) % n_flows);
+        const uint32_t f = flow_of ? flow_of[i] : implicit_flow(flow_origin, i, n_flows);
         // with flow_of, n_flows bounds the entry (pipck_update_fixed_n; UINT32_MAX:
         // trusted).  A stale entry must not turn into a checksum computed from
         // bytes outside the tables and written into the packet: the packet is
         // left exactly as it was -- edit bytes and checksum field -- and the
         // call reports PIPCK_ERANGE.
         if (flow_of && f >= n_flows) {
-            flow_refused(err);
+            refuse(err);
             return;
         }
         po = pseudo_old[f];

@@ -51,7 +51,7 @@ __global__ __launch_bounds__(256) void k_wave(const uint8_t* __restrict__ arena,
     } else {
         off = pkt * stride;
         L = len;
-        if (pseudo) flow = flow_of ? flow_of[pkt] : (uint32_t)((flow_origin + pkt) % n_flows);
+        if (pseudo) flow = flow_of ? flow_of[pkt] : implicit_flow(flow_origin, pkt, n_flows);
         // a flow_of entry past the table (n_flows bounds it in the _n forms): result 0
         bad = pseudo && flow_of && flow >= n_flows;
         if (bad) L = 0, flow = 0;
@@ -76,10 +76,10 @@ __global__ __launch_bounds__(256) void k_wave(const uint8_t* __restrict__ arena,
     if (lane == 0) {
         const uint32_t P = pseudo ? Pb + len_term(L) : 0u;
         if (VERIFY)
-            ok[pkt] = !bad && fold16(P + F) == 0xFFFFu;
+            ok[pkt] = packet_result<true>(P, F, bad);
         else
-            out[pkt] = bad ? (uint16_t)0 : finish(P, F);
-        if (bad && err) atomicOr(err, 1u << PIPCK_ERANGE);
+            out[pkt] = packet_result<false>(P, F, bad);
+        refuse(err, bad);
     }
 }
 
