@@ -54,9 +54,9 @@ const char* pipck_last_error(void);
  * checked) -- 1.0's single "ok == 3" meant verified.  1.2: the bounded _n forms
  * of the ragged, chain and ring calls.  1.3: the bounded _n forms of the
  * fixed-stride calls (pipck_checksum_fixed_n, pipck_verify_fixed_n,
- * pipck_update_fixed_n).  1.4: pipck_tx_fill_device. */
+ * pipck_update_fixed_n).  1.4: pipck_tx_fill_device.  1.5: pipck_tx_fill_ring. */
 #define PIPCK_VERSION_MAJOR 1
-#define PIPCK_VERSION_MINOR 4
+#define PIPCK_VERSION_MINOR 5
 uint32_t pipck_version(void);
 
 /* ---- flows / pseudo-headers ------------------------------------------ */
@@ -603,6 +603,30 @@ int pipck_host_rx_verify_packed(pipck_ctx* ctx, const void* h_frames, const uint
 #define PIPCK_TX_UDP_ZERO_AS_ONES 1u /* flags bit 0 */
 int pipck_tx_fill_device(void* d_arena, uint64_t arena_bytes, const uint16_t* d_lens, const uint64_t* d_tile_off,
                          uint64_t n_packets, uint32_t flags, uint8_t* d_done, uint32_t* d_err, void* stream);
+
+/* The same fill for frames in the fixed-size slots of a TX ring in DEVICE
+ * memory -- where a generator, a forwarder or a re-stamper writes frames whose
+ * packed offsets it cannot know in advance.  Layout and arguments as
+ * pipck_rx_verify_ring_n: frame i of d_lens[i] bytes (0..65,535) at d_arena +
+ * i * slot_stride, the rest of each slot never read and never written; d_arena
+ * 16-byte aligned, readable and writable for n_slots * slot_stride bytes;
+ * slot_stride a multiple of 16 from 1,024 to 65,536.  For each frame the fields
+ * written, their values, d_done[i] (PIPCK_TX_IP_FILLED, PIPCK_TX_L4_FILLED) and
+ * the meaning of flags (PIPCK_TX_UDP_ZERO_AS_ONES) are those of
+ * pipck_tx_fill_device for the same bytes: the rule list above is the one
+ * definition.  Bounded on the device: a slot with d_lens[i] > slot_stride is
+ * neither read nor written, gets d_done[i] = 0, and d_err (optional, device
+ * u32) gets (1 << PIPCK_ERANGE).  PIPCK_EINVAL for a null d_arena, d_lens or
+ * d_done, a misaligned arena, a stride outside the rule above or unknown bits
+ * in flags; n_slots == 0 returns PIPCK_OK.  One kernel on `stream`,
+ * asynchronous, with no host-side allocation and no per-ring state (capturable
+ * in a graph; the schedule feedback of pipck_rx_verify_ring_n is not used):
+ * blocks of 64 slots read only the frame bytes of their slots, then a lane per
+ * slot parses the headers and stores each field with one aligned 16-bit store.
+ * The slots of one call must not be read or written by other work on the
+ * device while it runs. */
+int pipck_tx_fill_ring(void* d_arena, uint64_t slot_stride, const uint16_t* d_lens, uint64_t n_slots,
+                       uint32_t flags, uint8_t* d_done, uint32_t* d_err, void* stream);
 
 #ifdef __cplusplus
 }

@@ -110,6 +110,9 @@ int launch_ring_rx(const void* d_arena, uint64_t stride, const uint16_t* d_lens,
                    uint32_t* d_err, hipStream_t s);
 int launch_packedb_rx(const void* d_arena, uint64_t arena_bytes, const uint16_t* d_lens, const uint64_t* d_tile_off,
                       uint64_t n, uint8_t* d_ok, uint32_t* d_err, hipStream_t s);
+// pipck_tx_fill_ring (pipck_txring.hip): k_ring's streams with the TX fill at each block's end.
+int launch_ring_tx(void* d_arena, uint64_t stride, const uint16_t* d_lens, uint64_t n, uint32_t flags,
+                   uint8_t* d_done, uint32_t* d_err, hipStream_t s);
 
 // The one-packet-per-wave measurement arm (pipck_wave.hip; TuneView::wave_arm()):
 // fixed strides (desc == false) or descriptors.

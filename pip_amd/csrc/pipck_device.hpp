@@ -142,6 +142,13 @@ __device__ __forceinline__ void store_result8(buf_t r, uint32_t byte_off, uint32
 __device__ __forceinline__ void store_field8(buf_t r, uint32_t byte_off, uint32_t v) {
     __builtin_amdgcn_raw_buffer_store_b8((uint8_t)v, r, (int)byte_off, 0, 0);
 }
+// The same for k_ring_tx (pipck_tx_fill_ring), whose fields sit at even
+// addresses inside one 16-byte chunk (the derivation is at the kernel): one
+// 16-bit store per field, the value as memory's little-endian halfword
+// (bswap16 of the big-endian field), with the same default policy.
+__device__ __forceinline__ void store_field16(buf_t r, uint32_t byte_off, uint32_t v) {
+    __builtin_amdgcn_raw_buffer_store_b16((uint16_t)v, r, (int)byte_off, 0, 0);
+}
 
 // ---- wave-level helpers (wave64) shared by the streaming kernels
 __device__ __forceinline__ void wave_sync() {

@@ -2,7 +2,8 @@
 // to be sent (pipck_tx_fill_device, include/pipck.h "TX checksum fill").  The TX
 // mirror of pipck_rxparse.hpp: k_packedb_tx (pipck_packedb.hip) calls
 // tx_from_window at each tile's end with the frame sum it has just streamed and
-// the header window it captured, and stores the two fields this returns -- the
+// the header window it captured -- as k_ring_tx (pipck_txring.hip) does at each
+// block's end for frames in ring slots -- and stores the two fields this returns: the
 // bytes pip's TX path writes (th_sum, pip/protocol/pip_tcp_packet.cpp:124-134;
 // uh_sum, pip/protocol/pip_udp.cpp:40-61; ip_sum, pip/pip_netif.cpp:80-97).
 //

@@ -378,6 +378,23 @@ def tx_fill_device(arena, lens, tile_off, n: int | None = None, flags: int = 0, 
     return done
 
 
+def tx_fill_ring(ring, stride: int, lens, n: int | None = None, flags: int = 0, done=None, err=None):
+    """IP frames about to be sent, in the fixed-size slots of a device ring (pipck_tx_fill_ring):
+    frame i of lens[i] bytes at ring[i * stride]; both checksum fields of every frame are stored
+    in place by tx_fill_device's rules, the rest of each slot neither read nor written; returns
+    the PIPCK_TX_* bits per slot (uint8).  A slot length past the stride is refused on the device
+    (done 0, nothing stored, 1 << PIPCK_ERANGE OR-ed into err, an optional device int32)."""
+    torch = _torch()
+    n = lens.numel() if n is None else n
+    if n * stride > _nbytes(ring) or n > lens.numel():
+        raise ValueError("ring smaller than n * stride, or fewer lengths than slots")
+    if done is None:
+        done = torch.empty(n, dtype=torch.uint8, device=ring.device)
+    call("pipck_tx_fill_ring", _ptr(ring), stride, _ptr(lens), n, flags, _ptr(done), _ptr(err),
+         current_stream(ring.device))
+    return done
+
+
 def packed_bytes_index(lens, n: int | None = None):
     """tile_off for a byte-packed batch: the byte offset of every 64th packet (u64 as int64) + the total."""
     torch = _torch()

@@ -23,6 +23,16 @@ two RX medians give the run-to-run spread the TX / RX ratio is read against.  Th
 frames already carry pip's checksums, so the TX leg must leave the arena byte for
 byte as it was (checked), whatever it costs to store them again.  One JSON line
 per mix, with the library's sha256.
+
+    python tools/rx_device_bench.py --tx-rings
+
+does the same for pipck_tx_fill_ring (k_ring_tx) on the five rings of --rings
+(engine.gen_rx_ring: sparse 9,216, dense 1,536, dense 9,216, short 2,048, short
+1,024): the yardstick is pipck_rx_verify_ring_n's k_ring on the same ring (tune
+ring_adapt=False: k_ring at every fill) in the same process, the legs RX, TX, RX
+rotating over six rounds of 20 launches after 40 warm-up launches each; every TX
+launch stores every field again and must leave the ring as it was (checked).
+One JSON line per ring, with the device's PCI bus id and the library's sha256.
 """
 from __future__ import annotations
 
@@ -115,12 +125,83 @@ def tx_vs_rx(a):
         torch.cuda.empty_cache()
 
 
+# the five rings of DESIGN.md section 9 f2: (tag, slot stride, L4 length (0 = Zipf), slots per --packets slot)
+BENCH_RINGS = (("ring_sparse_9216", 9216, 0, 1), ("ring_dense_1536", 1536, 1480, 1), ("ring_dense_9216", 9216, 8900, 2),
+               ("ring_short_2048", 2048, 200, 1), ("ring_short_1024", 1024, 100, 1))
+
+
+def tx_rings(a):
+    """The --tx-rings legs (see the module docstring)."""
+    import hashlib
+
+    import numpy as np
+    import torch
+
+    from bench import last_kernel
+    from pip_amd import _lib, engine
+    from size_scan import timed_b2b
+
+    engine.require_gpu()
+    sha = hashlib.sha256(_lib.LIBPIPCK.read_bytes()).hexdigest()  # the build this process loaded
+    box = engine.pci_bus_id(torch.cuda.current_device())
+    engine.tune(ring_adapt=False)  # RX: k_ring at every fill (k_ring_tx reads no adapt bit)
+    try:
+        for tag, stride, l4_len, div in [r for r in BENCH_RINGS if r[0] in a.rings.split(",")]:
+            m = a.packets // div
+            ring, lens, _ = engine.gen_rx_ring(m, 11, stride, l4_len=l4_len)
+            fbytes = int((lens.to(torch.int64) & 0xFFFF).sum().item())
+            ok = torch.empty(m, dtype=torch.uint8, device="cuda")
+            done = torch.empty(m, dtype=torch.uint8, device="cuda")
+            before = ring.clone()
+
+            def rx():
+                engine.call("pipck_rx_verify_ring_n", engine._ptr(ring), stride, engine._ptr(lens), m, engine._ptr(ok),
+                            None, engine.current_stream())
+
+            def tx():
+                engine.call("pipck_tx_fill_ring", engine._ptr(ring), stride, engine._ptr(lens), m, 0,
+                            engine._ptr(done), None, engine.current_stream())
+
+            legs = [("rx_a", rx), ("tx", tx), ("rx_b", rx)]
+            ms = {k: [] for k, _ in legs}
+            kern = {}
+            for rnd in range(a.rounds):
+                for name, fn in legs[rnd % 3:] + legs[:rnd % 3]:
+                    for _ in range(a.warm):
+                        fn()
+                    ms[name].append(timed_b2b(fn, a.iters))
+                    kern[name] = last_kernel().split("(")[0]
+            unchanged = bool(torch.equal(ring, before))
+            med = {k: statistics.median(v) for k, v in ms.items()}
+            rx_mean = (med["rx_a"] + med["rx_b"]) / 2
+            hist = lambda t: {int(k): int(c) for k, c in zip(*np.unique(t.cpu().numpy(), return_counts=True))}  # noqa: E731
+            stores = sum(c * bin(k).count("1") for k, c in hist(done).items())  # one 16-bit store per filled field
+            print(json.dumps({"what": "tx_fill_ring_vs_rx_verify_ring", "ring": tag, "slot_stride": stride,
+                              "l4_len": l4_len or "zipf", "frames": m, "frame_bytes": fbytes, "slot_bytes": m * stride,
+                              "rx_kernel": kern["rx_a"], "tx_kernel": kern["tx"],
+                              **{k + "_ms": round(v, 4) for k, v in med.items()},
+                              **{k + "_rounds_ms": [round(x, 4) for x in v] for k, v in ms.items()},
+                              "tx_over_rx": round(med["tx"] / rx_mean, 4),
+                              "rx_spread": round(abs(med["rx_a"] - med["rx_b"]) / rx_mean, 4),
+                              "tx_minus_rx_ps_per_frame": round((med["tx"] - rx_mean) * 1e9 / m, 1),
+                              "field_stores": stores, "tx_GBps": round((fbytes + m) / med["tx"] / 1e6, 1),
+                              "tx_frac": round((fbytes + m) / med["tx"] / 1e6 / 8000, 4),
+                              "warm": a.warm, "rounds": a.rounds, "iters": a.iters,
+                              "ring_unchanged_by_tx": unchanged, "done": hist(done), "verdicts": hist(ok),
+                              "pci_bus_id": box, "lib_sha256": sha}), flush=True)
+            assert unchanged, "pipck_tx_fill_ring changed frames that already carried pip's checksums"
+            del ring, before, lens, ok, done
+            torch.cuda.empty_cache()
+    finally:
+        engine.tune()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--packets", type=int, default=8 << 20)
-    ap.add_argument("--iters", type=int, default=10)
+    ap.add_argument("--iters", type=int, default=None, help="timed launches per round (10; --tx-rings: 20)")
     ap.add_argument("--warm", type=int, default=40)
-    ap.add_argument("--rounds", type=int, default=3)
+    ap.add_argument("--rounds", type=int, default=None, help="rounds per arm (3; --tx-rings: 6)")
     ap.add_argument("--rings", default="ring_sparse_9216,ring_dense_1536,ring_dense_9216,ring_short_2048,ring_short_1024")
     ap.add_argument("--tune", default="{}", help="engine.tune kwargs for the packed arms and the default (groups) ring arm, JSON")
     ap.add_argument("--skip-packed", action="store_true", help="rings only")
@@ -129,7 +210,13 @@ def main():
     ap.add_argument("--tunes", default="{}", help='JSON {"NAME": engine.tune kwargs} for groups:NAME arms')
     ap.add_argument("--tx-mixes", default="",
                     help="L4 lengths (0 = Zipf) for the TX-against-RX legs; nothing else runs")
+    ap.add_argument("--tx-rings", action="store_true",
+                    help="pipck_tx_fill_ring against k_ring on the --rings; nothing else runs")
     a = ap.parse_args()
+    if a.tx_rings:
+        a.iters, a.rounds = a.iters or 20, a.rounds or 6
+        return tx_rings(a)
+    a.iters, a.rounds = a.iters or 10, a.rounds or 3
     if a.tx_mixes:
         return tx_vs_rx(a)
     tune_default = json.loads(a.tune)
