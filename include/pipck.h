@@ -54,9 +54,10 @@ const char* pipck_last_error(void);
  * checked) -- 1.0's single "ok == 3" meant verified.  1.2: the bounded _n forms
  * of the ragged, chain and ring calls.  1.3: the bounded _n forms of the
  * fixed-stride calls (pipck_checksum_fixed_n, pipck_verify_fixed_n,
- * pipck_update_fixed_n).  1.4: pipck_tx_fill_device.  1.5: pipck_tx_fill_ring. */
+ * pipck_update_fixed_n).  1.4: pipck_tx_fill_device.  1.5: pipck_tx_fill_ring.
+ * 1.6: pipck_fwd_rewrite_ring. */
 #define PIPCK_VERSION_MAJOR 1
-#define PIPCK_VERSION_MINOR 5
+#define PIPCK_VERSION_MINOR 6
 uint32_t pipck_version(void);
 
 /* ---- flows / pseudo-headers ------------------------------------------ */
@@ -627,6 +628,116 @@ int pipck_tx_fill_device(void* d_arena, uint64_t arena_bytes, const uint16_t* d_
  * device while it runs. */
 int pipck_tx_fill_ring(void* d_arena, uint64_t slot_stride, const uint16_t* d_lens, uint64_t n_slots,
                        uint32_t flags, uint8_t* d_done, uint32_t* d_err, void* stream);
+
+/* ---- NAT and TTL rewrite of frames in a device ring ---------------------- */
+/* A forwarder sends on a frame it has just verified with a few header fields
+ * changed: the TTL or hop limit decremented (RFC 1812), addresses and ports
+ * replaced (NAT, RFC 3022).  pipck_fwd_rewrite_ring does that for the frames of
+ * a ring in DEVICE memory, from their headers alone: it stores the fields a
+ * rule names and updates the IPv4 header checksum and the TCP / UDP / ICMPv6
+ * checksum INCREMENTALLY (RFC 1624 eqn. 3) over the words of those fields.  So
+ *   - the frame's one's-complement sums are preserved: a checksum that
+ *     verified before the call verifies after it, and one that failed still
+ *     fails -- a corrupted frame does not leave the box valid, as it would
+ *     after rewriting the bytes and calling pipck_tx_fill_ring;
+ *   - link padding and payload are never read: per frame the call reads the
+ *     first min(length, 96) bytes (in aligned 16-byte chunks) and, only where
+ *     an IPv6 extension chain carries the L4 fields past them, those headers;
+ *   - with PIPCK_FWD_DEC_TTL the call is not idempotent: every call decrements.
+ * Layout and host-side argument rules are those of pipck_tx_fill_ring: frame i
+ * of d_lens[i] bytes at d_arena + i * slot_stride, d_arena 16-byte aligned,
+ * slot_stride a multiple of 16 from 1,024 to 65,536, bytes of a slot past its
+ * frame never read and never written.  d_rules is a table of n_rules rules,
+ * 16-byte aligned; slot i takes rule d_rule_of ? d_rule_of[i] : 0.  d_done[i]
+ * receives 0 or exactly one of PIPCK_FWD_DONE, PIPCK_FWD_EXPIRED,
+ * PIPCK_FWD_UNHANDLED.  Per slot, in this order -- the first rule that applies
+ * decides, and a frame is rewritten entirely or not at all
+ * (tests/fwd_reference.py restates steps 2 to 6 in plain integer arithmetic and
+ * the kernel is held to it byte for byte):
+ *   1. Refusals, bounded on the device before any access they govern:
+ *      d_lens[i] > slot_stride, or a rule index >= n_rules other than
+ *      PIPCK_FWD_NO_RULE.  The slot is neither read nor written, d_done[i] = 0
+ *      and d_err (optional, device u32) gets (1 << PIPCK_ERANGE); an index
+ *      past the table never reads the table.  PIPCK_FWD_NO_RULE is not an
+ *      error: the slot is neither read nor written, d_done[i] = 0, no error
+ *      bit -- how a caller passes over frames that RX verification rejected.
+ *   2. An invalid rule -- unknown ops bits, a family that is none of 0, 4, 6,
+ *      or family 0 with PIPCK_FWD_SET_SRC or PIPCK_FWD_SET_DST: the frame is
+ *      untouched, d_done[i] = 0, d_err gets (1 << PIPCK_EINVAL).
+ *   3. A malformed frame, by the rules of pipck_tx_fill_device (under 20 bytes;
+ *      a version that is neither 4 nor 6; IPv4 with IHL < 5, total length <
+ *      header length or total length > frame length; version 6 under 40 bytes
+ *      or with 40 + payload length > frame length): untouched, d_done[i] = 0,
+ *      no error bit.
+ *   4. PIPCK_FWD_DEC_TTL with a TTL (IPv4 byte 8) or hop limit (IPv6 byte 7)
+ *      of 0 or 1: untouched, PIPCK_FWD_EXPIRED.  The host answers with ICMP.
+ *   5. PIPCK_FWD_UNHANDLED, untouched, when
+ *      - the rule's family is 4 or 6 and differs from the frame's version;
+ *      - the rule sets an address or a port and the upper layer cannot be
+ *        located -- it is located exactly as pipck_tx_fill_device locates it,
+ *        so not for an IPv4 fragment (ip_off & 0x3FFF), an IPv6 fragment
+ *        header with an offset or M, a routing header, a ninth extension
+ *        header, or an extension header that does not fit in the payload;
+ *      - the rule sets a port and the protocol is not TCP or UDP;
+ *      - the rule sets an address and the protocol is none of TCP, UDP, ICMP
+ *        over IPv4, ICMPv6 over IPv6;
+ *      - the L4 length is under 20 (TCP) or under 8 (UDP, ICMP, ICMPv6).
+ *      A rule with PIPCK_FWD_DEC_TTL alone never looks at the upper layer:
+ *      fragments and any protocol are handled.
+ *   6. Otherwise PIPCK_FWD_DONE.  Every field the rule names is stored:
+ *      DEC_TTL stores the old value minus one; the source and destination
+ *      address go to IPv4 bytes 12-15 and 16-19 (the first 4 bytes of src /
+ *      dst) or IPv6 bytes 8-23 and 24-39; the ports to message offsets 0 and
+ *      2.  Each checksum field that covers a named field is updated over
+ *      exactly the 16-bit big-endian words of the named fields, whether or not
+ *      their value changes:
+ *          s   = (~HC & 0xFFFF) + sum(~old_k & 0xFFFF) + sum(new_k)    (exact)
+ *          HC' = ~fold(s) & 0xFFFF     fold: end-around carry until s < 0x10000
+ *      - The IPv4 header field (bytes 10-11): bytes 8-9 (TTL with protocol)
+ *        for DEC_TTL, the address words for SET_SRC / SET_DST.  IPv6 has none.
+ *      - The L4 field (message offset 16 for TCP, 6 for UDP, 2 for ICMPv6):
+ *        the address words, through the pseudo-header, and for TCP and UDP the
+ *        port words.  ICMP over IPv4 has no pseudo-header: its field is not
+ *        touched.  A checksum field whose word list is empty is not touched.
+ *      - UDP over IPv4 with a zero field keeps its zero (RFC 3022 section
+ *        4.1); addresses and ports are still rewritten.  UDP over IPv6 with a
+ *        zero field is updated like any value.
+ *      - With PIPCK_FWD_UDP_ZERO_AS_ONES in flags, a UDP field that updates to
+ *        0x0000 is stored as 0xFFFF, over IPv4 or IPv6.
+ *      No byte outside the named fields and those two checksum fields changes
+ *      value.  ICMP error payloads' embedded headers, the TCP / UDP length
+ *      fields, SCTP and DCCP are not handled.
+ * PIPCK_EINVAL (no launch) for a null d_arena, d_lens, d_done or d_rules,
+ * n_rules == 0, a rule table or an arena that is not 16-byte aligned, a stride
+ * outside the rule above or unknown bits in flags; n_slots == 0 returns
+ * PIPCK_OK.  One kernel on `stream`, asynchronous, with no host-side
+ * allocation and no per-ring state (capturable in a graph).  The slots of one
+ * call must not be read or written by other work on the device while it runs. */
+#define PIPCK_FWD_SET_SRC   1u   /* ops bits */
+#define PIPCK_FWD_SET_DST   2u
+#define PIPCK_FWD_SET_SPORT 4u
+#define PIPCK_FWD_SET_DPORT 8u
+#define PIPCK_FWD_DEC_TTL   16u
+#define PIPCK_FWD_UDP_ZERO_AS_ONES 1u   /* flags bit 0 */
+#define PIPCK_FWD_DONE      1u   /* d_done values, exclusive */
+#define PIPCK_FWD_EXPIRED   2u
+#define PIPCK_FWD_UNHANDLED 4u
+#define PIPCK_FWD_NO_RULE   0xFFFFFFFFu
+
+typedef struct pipck_fwd_rule {   /* 48 bytes, 16-byte aligned table */
+    uint32_t ops;        /* PIPCK_FWD_SET_* | PIPCK_FWD_DEC_TTL */
+    uint8_t  family;     /* 4 or 6: the frames it applies to; 0 = either, only without SET_SRC/SET_DST */
+    uint8_t  pad[3];
+    uint8_t  src[16];    /* wire bytes; IPv4 uses the first 4 */
+    uint8_t  dst[16];
+    uint8_t  sport[2];   /* wire bytes */
+    uint8_t  dport[2];
+    uint8_t  pad2[4];
+} pipck_fwd_rule;
+
+int pipck_fwd_rewrite_ring(void* d_arena, uint64_t slot_stride, const uint16_t* d_lens, uint64_t n_slots,
+                           const pipck_fwd_rule* d_rules, uint32_t n_rules, const uint32_t* d_rule_of,
+                           uint32_t flags, uint8_t* d_done, uint32_t* d_err, void* stream);
 
 #ifdef __cplusplus
 }

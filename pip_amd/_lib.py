@@ -42,6 +42,17 @@ class HSeg(C.Structure):
     _fields_ = [("ptr", _p), ("len", _u32)]
 
 
+class FwdRule(C.Structure):  # pipck_fwd_rule: 48 bytes
+    _fields_ = [("ops", _u32), ("family", _u8), ("pad", _u8 * 3), ("src", _u8 * 16), ("dst", _u8 * 16),
+                ("sport", _u8 * 2), ("dport", _u8 * 2), ("pad2", _u8 * 4)]
+
+
+FWD_SET_SRC, FWD_SET_DST, FWD_SET_SPORT, FWD_SET_DPORT, FWD_DEC_TTL = 1, 2, 4, 8, 16  # pipck_fwd_rule.ops
+FWD_UDP_ZERO_AS_ONES = 1  # flags bit 0
+FWD_DONE, FWD_EXPIRED, FWD_UNHANDLED = 1, 2, 4  # d_done values
+FWD_NO_RULE = 0xFFFFFFFF  # a d_rule_of entry: pass over the slot
+
+
 # name -> (restype, argtypes); must match include/pipck.h (checked by tests/test_abi.py)
 SIGNATURES = {
     "pipck_last_error": (C.c_char_p, []),
@@ -103,6 +114,7 @@ SIGNATURES = {
     "pipck_rx_verify_device": (_i32, [_p, _u64, _p, _p, _u64, _p, _p, _p]),
     "pipck_tx_fill_device": (_i32, [_p, _u64, _p, _p, _u64, _u32, _p, _p, _p]),
     "pipck_tx_fill_ring": (_i32, [_p, _u64, _p, _u64, _u32, _p, _p, _p]),
+    "pipck_fwd_rewrite_ring": (_i32, [_p, _u64, _p, _u64, _p, _u32, _p, _u32, _p, _p, _p]),
     "pipck_host_rx_verify_packed": (_i32, [_p, _p, _p, _u64, _p, C.POINTER(_u64)]),
     "pipck_rx_verify_ring": (_i32, [_p, _u64, _p, _u64, _p, _p]),
     "pipck_rx_verify_ring_n": (_i32, [_p, _u64, _p, _u64, _p, _p, _p]),

@@ -113,6 +113,10 @@ int launch_packedb_rx(const void* d_arena, uint64_t arena_bytes, const uint16_t*
 // pipck_tx_fill_ring (pipck_txring.hip): k_ring's streams with the TX fill at each block's end.
 int launch_ring_tx(void* d_arena, uint64_t stride, const uint16_t* d_lens, uint64_t n, uint32_t flags,
                    uint8_t* d_done, uint32_t* d_err, hipStream_t s);
+// pipck_fwd_rewrite_ring (pipck_fwd.hip): NAT and TTL rewrite of ring slots from their headers alone.
+int launch_ring_fwd(void* d_arena, uint64_t stride, const uint16_t* d_lens, uint64_t n, const pipck_fwd_rule* d_rules,
+                    uint32_t n_rules, const uint32_t* d_rule_of, uint32_t flags, uint8_t* d_done, uint32_t* d_err,
+                    hipStream_t s);
 
 // The one-packet-per-wave measurement arm (pipck_wave.hip; TuneView::wave_arm()):
 // fixed strides (desc == false) or descriptors.

@@ -16,6 +16,8 @@ import ctypes as C
 
 from . import _lib
 from ._lib import Desc, Flow4, Flow6, call, check, load  # noqa: F401  (re-exported)
+from ._lib import (FWD_DEC_TTL, FWD_DONE, FWD_EXPIRED, FWD_NO_RULE, FWD_SET_DPORT, FWD_SET_DST,  # noqa: F401
+                   FWD_SET_SPORT, FWD_SET_SRC, FWD_UDP_ZERO_AS_ONES, FWD_UNHANDLED)  # pipck_fwd_rewrite_ring's constants
 
 DESC_BYTES = C.sizeof(Desc)  # 16: u64 offset, u32 len, u32 flow
 
@@ -392,6 +394,64 @@ def tx_fill_ring(ring, stride: int, lens, n: int | None = None, flags: int = 0, 
         done = torch.empty(n, dtype=torch.uint8, device=ring.device)
     call("pipck_tx_fill_ring", _ptr(ring), stride, _ptr(lens), n, flags, _ptr(done), _ptr(err),
          current_stream(ring.device))
+    return done
+
+
+FWD_RULE_BYTES = C.sizeof(_lib.FwdRule)  # 48
+
+
+def fwd_rule_bytes(ops: int, family: int = 0, src=b"", dst=b"", sport=0, dport=0) -> bytes:
+    """One pipck_fwd_rule as its 48 bytes.  src / dst: the address's wire bytes (4 or 16; IPv4 uses
+    the first 4); sport / dport: a port number, or its 2 wire bytes.  Nothing is validated here:
+    the device refuses an invalid rule per slot (include/pipck.h)."""
+    def port(p):
+        return int(p).to_bytes(2, "big") if isinstance(p, int) else bytes(p)
+
+    src, dst, sp, dp = bytes(src), bytes(dst), port(sport), port(dport)
+    if len(src) > 16 or len(dst) > 16 or len(sp) != 2 or len(dp) != 2:
+        raise ValueError("an address has at most 16 bytes and a port 2")
+    out = (int(ops).to_bytes(4, "little") + bytes([family, 0, 0, 0]) + src.ljust(16, b"\0") + dst.ljust(16, b"\0") +
+           sp + dp + bytes(4))
+    assert len(out) == FWD_RULE_BYTES
+    return out
+
+
+def make_fwd_rules(rules, device=None):
+    """The rule table of fwd_rewrite_ring: uint8[n, 48] on `device` (default: the current one) from
+    a list of dicts (keys ops, family, src, dst, sport, dport, as fwd_rule_bytes takes them) or of
+    tuples in that order.  A fresh allocation, so 16-byte aligned."""
+    torch = _torch()
+    raw = b"".join(fwd_rule_bytes(**r) if isinstance(r, dict) else fwd_rule_bytes(*r) for r in rules)
+    if not raw:
+        raise ValueError("a rule table needs at least one rule")
+    dev = torch.device("cuda", torch.cuda.current_device()) if device is None else device
+    return torch.frombuffer(bytearray(raw), dtype=torch.uint8).view(-1, FWD_RULE_BYTES).to(dev)
+
+
+def fwd_rewrite_ring(ring, stride: int, lens, rules, rule_of=None, n: int | None = None, flags: int = 0, done=None,
+                     err=None):
+    """NAT and TTL rewrite of the frames in the fixed-size slots of a device ring, from their
+    headers alone (pipck_fwd_rewrite_ring): slot i takes rule rules[rule_of[i]] (rule 0 without
+    rule_of; FWD_NO_RULE passes over the slot); the fields the rule names are stored and the IPv4
+    header and L4 checksum fields updated incrementally (RFC 1624), so a checksum that verified
+    still verifies and one that failed still fails.  Returns the done bytes (uint8): FWD_DONE,
+    FWD_EXPIRED, FWD_UNHANDLED or 0.  rules: make_fwd_rules' tensor; rule_of: int32 / uint32 per
+    slot.  A slot length past the stride or a rule index past the table is refused on the device
+    (done 0, nothing stored, 1 << PIPCK_ERANGE OR-ed into err, an optional device int32); an
+    invalid rule sets 1 << PIPCK_EINVAL there."""
+    torch = _torch()
+    n = lens.numel() if n is None else n
+    if n * stride > _nbytes(ring) or n > lens.numel():
+        raise ValueError("ring smaller than n * stride, or fewer lengths than slots")
+    if rules.dtype != torch.uint8 or rules.dim() != 2 or rules.shape[1] != FWD_RULE_BYTES or rules.shape[0] == 0 or \
+            not rules.is_contiguous() or rules.device != ring.device:
+        raise ValueError("rules must be make_fwd_rules' uint8[n, 48] tensor on the ring's device")
+    if rule_of is not None and (rule_of.element_size() != 4 or n > rule_of.numel()):
+        raise ValueError("rule_of must hold one 32-bit index per slot")
+    if done is None:
+        done = torch.empty(n, dtype=torch.uint8, device=ring.device)
+    call("pipck_fwd_rewrite_ring", _ptr(ring), stride, _ptr(lens), n, _ptr(rules), rules.shape[0], _ptr(rule_of),
+         flags, _ptr(done), _ptr(err), current_stream(ring.device))
     return done
 
 

@@ -33,6 +33,18 @@ ring_adapt=False: k_ring at every fill) in the same process, the legs RX, TX, RX
 rotating over six rounds of 20 launches after 40 warm-up launches each; every TX
 launch stores every field again and must leave the ring as it was (checked).
 One JSON line per ring, with the device's PCI bus id and the library's sha256.
+
+    python tools/rx_device_bench.py --fwd-rings
+
+times pipck_fwd_rewrite_ring (k_fwd_ring; one rule per family with all five ops,
+PIPCK_FWD_UDP_ZERO_AS_ONES) against pipck_tx_fill_ring and k_ring on the same
+five rings in one process: the legs RX, rewrite, TX, RX rotate over eight rounds
+of 20 launches after 40 warm-up launches each.  The rewrite reads header lines
+only, so its time follows the slots, not the frame bytes.  Every frame first gets
+TTL / hop limit 255 and its checksums filled again, and every leg starts from a
+copy of that ring: a rewrite decrements every TTL, and none may expire within a
+leg.  After a leg of rewrites pipck_rx_verify_ring_n must give every frame the
+verdict it had (checked).  One JSON line per ring.
 """
 from __future__ import annotations
 
@@ -196,12 +208,115 @@ def tx_rings(a):
         engine.tune()
 
 
+def fwd_rings(a):
+    """The --fwd-rings legs (see the module docstring)."""
+    import hashlib
+
+    import numpy as np
+    import torch
+
+    from bench import last_kernel
+    from pip_amd import _lib, engine
+    from size_scan import timed_b2b
+
+    engine.require_gpu()
+    sha = hashlib.sha256(_lib.LIBPIPCK.read_bytes()).hexdigest()  # the build this process loaded
+    box = engine.pci_bus_id(torch.cuda.current_device())
+    all_ops = (engine.FWD_SET_SRC | engine.FWD_SET_DST | engine.FWD_SET_SPORT | engine.FWD_SET_DPORT |
+               engine.FWD_DEC_TTL)
+    rules = engine.make_fwd_rules([
+        dict(ops=all_ops, family=4, src=bytes([203, 0, 113, 7]), dst=bytes([198, 51, 100, 9]), sport=40001, dport=53),
+        dict(ops=all_ops, family=6, src=bytes.fromhex("20010db885a3000000008a2e03707334"),
+             dst=bytes.fromhex("20010db8000000000000ff0000428329"), sport=40001, dport=53)])
+    engine.tune(ring_adapt=False)  # RX: k_ring at every fill
+    try:
+        for tag, stride, l4_len, div in [r for r in BENCH_RINGS if r[0] in a.rings.split(",")]:
+            m = a.packets // div
+            ring, lens, kind = engine.gen_rx_ring(m, 11, stride, l4_len=l4_len)
+            fbytes = int((lens.to(torch.int64) & 0xFFFF).sum().item())
+            ok = torch.empty(m, dtype=torch.uint8, device="cuda")
+            done = torch.empty(m, dtype=torch.uint8, device="cuda")
+            fdone = torch.empty(m, dtype=torch.uint8, device="cuda")
+            v6 = kind == 3
+            rule_of = v6.to(torch.int32)
+            # TTL / hop limit 255 (a leg's launches never reach 1), the checksums filled again
+            rows = ring.view(m, stride)
+            rows[torch.nonzero(~v6).flatten(), 8] = 255
+            rows[torch.nonzero(v6).flatten(), 7] = 255
+            engine.tx_fill_ring(ring, stride, lens, m)
+            before = ring.clone()
+            assert a.warm + a.iters < 250
+
+            def rx():
+                engine.call("pipck_rx_verify_ring_n", engine._ptr(ring), stride, engine._ptr(lens), m, engine._ptr(ok),
+                            None, engine.current_stream())
+
+            def tx():
+                engine.call("pipck_tx_fill_ring", engine._ptr(ring), stride, engine._ptr(lens), m, 0,
+                            engine._ptr(done), None, engine.current_stream())
+
+            def fwd():
+                engine.call("pipck_fwd_rewrite_ring", engine._ptr(ring), stride, engine._ptr(lens), m,
+                            engine._ptr(rules), 2, engine._ptr(rule_of), engine.FWD_UDP_ZERO_AS_ONES,
+                            engine._ptr(fdone), None,
+                            engine.current_stream())
+
+            rx()
+            verdicts_before = ok.clone()
+            legs = [("rx_a", rx), ("fwd", fwd), ("tx", tx), ("rx_b", rx)]
+            ms = {k: [] for k, _ in legs}
+            kern = {}
+            for rnd in range(a.rounds):
+                for name, fn in legs[rnd % 4:] + legs[:rnd % 4]:
+                    ring.copy_(before)  # every leg on the same bytes: a rewrite decrements every TTL
+                    for _ in range(a.warm):
+                        fn()
+                    ms[name].append(timed_b2b(fn, a.iters))
+                    kern[name] = last_kernel().split("(")[0]
+            # the sums are preserved: after a leg of rewrites every frame has the verdict it had
+            ring.copy_(before)
+            for _ in range(a.warm + a.iters):
+                fwd()
+            rx()
+            kept = bool(torch.equal(ok, verdicts_before))
+            med = {k: statistics.median(v) for k, v in ms.items()}
+            rx_mean = (med["rx_a"] + med["rx_b"]) / 2
+            hist = lambda t: {int(k): int(c) for k, c in zip(*np.unique(t.cpu().numpy(), return_counts=True))}  # noqa: E731
+            n_done = int((fdone == engine.FWD_DONE).sum().item())
+            # lines a rewritten slot touches: the window's (read) are the written ones too -- the header
+            # fields of these frames lie in the slot's first 128 bytes
+            lines = int(((lens.to(torch.int64) & 0xFFFF).clamp(max=96) + 127).div(128, rounding_mode="floor").sum().item())
+            print(json.dumps({"what": "fwd_rewrite_ring_vs_tx_fill_ring_vs_rx_verify_ring", "ring": tag,
+                              "slot_stride": stride, "l4_len": l4_len or "zipf", "frames": m, "frame_bytes": fbytes,
+                              "slot_bytes": m * stride, "rx_kernel": kern["rx_a"], "tx_kernel": kern["tx"],
+                              "fwd_kernel": kern["fwd"],
+                              **{k + "_ms": round(v, 4) for k, v in med.items()},
+                              **{k + "_rounds_ms": [round(x, 4) for x in v] for k, v in ms.items()},
+                              "fwd_over_tx": round(med["fwd"] / med["tx"], 4),
+                              "fwd_over_rx": round(med["fwd"] / rx_mean, 4),
+                              "tx_over_rx": round(med["tx"] / rx_mean, 4),
+                              "rx_spread": round(abs(med["rx_a"] - med["rx_b"]) / rx_mean, 4),
+                              "fwd_spread": round((max(ms["fwd"]) - min(ms["fwd"])) / med["fwd"], 4),
+                              "fwd_ps_per_frame": round(med["fwd"] * 1e9 / m, 1),
+                              "fwd_Mframes_per_s": round(m / med["fwd"] / 1e3, 1),
+                              "window_lines": lines, "fwd_line_GBps": round(lines * 128 / med["fwd"] / 1e6, 1),
+                              "warm": a.warm, "rounds": a.rounds, "iters": a.iters,
+                              "verdicts_kept_by_fwd": kept, "fwd_done": hist(fdone), "frames_done": n_done,
+                              "tx_done": hist(done), "verdicts": hist(verdicts_before),
+                              "pci_bus_id": box, "lib_sha256": sha}), flush=True)
+            assert kept, "pipck_fwd_rewrite_ring changed an RX verdict"
+            del ring, rows, before, lens, ok, done, fdone, rule_of, verdicts_before
+            torch.cuda.empty_cache()
+    finally:
+        engine.tune()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--packets", type=int, default=8 << 20)
-    ap.add_argument("--iters", type=int, default=None, help="timed launches per round (10; --tx-rings: 20)")
+    ap.add_argument("--iters", type=int, default=None, help="timed launches per round (10; --tx-rings, --fwd-rings: 20)")
     ap.add_argument("--warm", type=int, default=40)
-    ap.add_argument("--rounds", type=int, default=None, help="rounds per arm (3; --tx-rings: 6)")
+    ap.add_argument("--rounds", type=int, default=None, help="rounds per arm (3; --tx-rings: 6; --fwd-rings: 8)")
     ap.add_argument("--rings", default="ring_sparse_9216,ring_dense_1536,ring_dense_9216,ring_short_2048,ring_short_1024")
     ap.add_argument("--tune", default="{}", help="engine.tune kwargs for the packed arms and the default (groups) ring arm, JSON")
     ap.add_argument("--skip-packed", action="store_true", help="rings only")
@@ -212,7 +327,12 @@ def main():
                     help="L4 lengths (0 = Zipf) for the TX-against-RX legs; nothing else runs")
     ap.add_argument("--tx-rings", action="store_true",
                     help="pipck_tx_fill_ring against k_ring on the --rings; nothing else runs")
+    ap.add_argument("--fwd-rings", action="store_true",
+                    help="pipck_fwd_rewrite_ring against pipck_tx_fill_ring and k_ring on the --rings; nothing else runs")
     a = ap.parse_args()
+    if a.fwd_rings:
+        a.iters, a.rounds = a.iters or 20, a.rounds or 8
+        return fwd_rings(a)
     if a.tx_rings:
         a.iters, a.rounds = a.iters or 20, a.rounds or 6
         return tx_rings(a)
