@@ -1320,7 +1320,8 @@ __global__ __launch_bounds__(64) void k_packed(const uint8_t* __restrict__ arena
     // `lead` chunks before it (the previous tile's last bytes) are loaded and
     // zeroed, and packet 0 of the tile is streamed as if it began there, so
     // every 1 KiB row is 8 whole lines and no line is fetched by two rows of a
-    // tile (tune flags bit 30: the r02 grid from the tile's first chunk).
+    // tile (tune flags bit 30: the r02 grid from the tile's first chunk; bit 4
+    // too: the lookup path sums every chunk it is given and zeroes no lead).
     const uint32_t nch = (len + 15) >> 4;
     const uint32_t nv = (uint32_t)min<uint64_t>(64, n - tile * 64);
     // The tile's chunks [tc0, tc0 + its chunk count) must lie in the arena
@@ -1338,7 +1339,8 @@ __global__ __launch_bounds__(64) void k_packed(const uint8_t* __restrict__ arena
         return;
     }
     const uintptr_t tbase = (uintptr_t)arena + 16ull * tc0;
-    const uint32_t lead = (__all(nch <= kTinyChunks) || (kflags & kPackedNoAlign)) ? 0u : (uint32_t)(tbase >> 4) & 7u;
+    const uint32_t lead = (__all(nch <= kTinyChunks) || (kflags & (kPackedNoAlign | kNoPackedTiles)))
+                              ? 0u : (uint32_t)(tbase >> 4) & 7u;
     const uint32_t nch_s = nch + (lane == 0 ? lead : 0u);
     const uint32_t excl = wave_incl_scan(nch_s) - nch_s;
     const uintptr_t addr = tbase - 16u * lead + 16ull * excl;

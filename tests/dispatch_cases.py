@@ -5,8 +5,11 @@ A GROUP is one entry point on one batch shape; a KNOB is one setting of the
 internal tuning words (pipck_testing.h).  run_group makes one launch per knob and
 returns {knob id: [return code, kernel name]}, the name as pipck_last_launch
 gives it, cut at the closing '>' of its template arguments (None when the call
-launched nothing).  No result is looked at: every output goes to a scratch
+launched nothing).  run_group looks at no result: every output goes to a scratch
 buffer, and the measurement bits (21-23, the in-place probe) compute none.
+tests/test_gpu_dispatch_results.py makes the same launches, knob for knob
+(apply_knob / reset_knobs), on batches with real contents and holds every result
+to a reference; tests/dispatch_results.py has those contents and references.
 
 Run as a program, this writes the table a build produces as JSON:
 
@@ -200,21 +203,38 @@ def last_kernel() -> str:
     return buf.value.decode().split("(")[0]
 
 
-def run_group(batches: Batches, group: str) -> dict[str, list]:
+def apply_knob(k: dict, xw: bool) -> bool:
+    """Set the tuning words of knob k (pipck_tune, pipck_tune_probes, pipck_tune_ring, the XCD weights).
+    xw: whether the XCD weights are on now; returns whether they are on afterwards."""
     from pip_amd import _lib, engine
 
     lib = _lib.load()
+    lib.pipck_tune(k["lanes"], k["loads"], k["blocks"], k["flags"])
+    lib.pipck_tune_probes(k["probes"])
+    lib.pipck_tune_ring(k["ring"])
+    if k["xw"] != xw:  # (a synchronous copy to the device: only when it changes)
+        xw = k["xw"]
+        engine.tune_xcd_weights([7] * 8 if xw else None, 7 if xw else 0)
+    return xw
+
+
+def reset_knobs() -> None:
+    """Every tuning word back to its default."""
+    from pip_amd import engine
+
+    engine.tune_xcd_weights(None, 0)
+    engine.tune()
+
+
+def run_group(batches: Batches, group: str) -> dict[str, list]:
+    from pip_amd import _lib
+
     launch = batches.launcher(group)
     got = {}
     xw = False
     try:
         for name, k in knobs_of(group).items():
-            lib.pipck_tune(k["lanes"], k["loads"], k["blocks"], k["flags"])
-            lib.pipck_tune_probes(k["probes"])
-            lib.pipck_tune_ring(k["ring"])
-            if k["xw"] != xw:  # (a synchronous copy to the device: only when it changes)
-                xw = k["xw"]
-                engine.tune_xcd_weights([7] * 8 if xw else None, 7 if xw else 0)
+            xw = apply_knob(k, xw)
             try:
                 launch()
                 got[name] = [0, last_kernel()]
@@ -222,8 +242,7 @@ def run_group(batches: Batches, group: str) -> dict[str, list]:
                 got[name] = [ex.rc, None]
         batches.torch.cuda.synchronize()
     finally:
-        engine.tune_xcd_weights(None, 0)
-        engine.tune()
+        reset_knobs()
     return got
 
 
