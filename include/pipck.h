@@ -87,6 +87,23 @@ int pipck_flows4_prepare(const pipck_flow4* d_flows, uint32_t n_flows, uint32_t*
 int pipck_flows6_prepare(const pipck_flow6* d_flows, uint32_t n_flows, uint32_t* d_pseudo, void* stream);
 
 /* ---- batch ABI (device pointers, stream-ordered) ----------------------- */
+/* Streams and graphs.  Every call of this section that takes device pointers
+ * and a stream only enqueues work on that stream -- kernels, and for
+ * pipck_rx_verify_ring_n at most one memset -- and returns without waiting for
+ * it: no host synchronisation, no work on any other stream, d_err OR-ed by the
+ * kernels (never stored).  All of them may be captured into a graph
+ * (hipStreamBeginCapture on `stream`) and the graph replayed on other
+ * contents at the same addresses: pipck_flows4/6_prepare, the fixed, ragged,
+ * packed, byte-packed and chain checksum / verify calls with and without _n,
+ * pipck_packed_index, pipck_packed_bytes_index, pipck_update_fixed{,_n},
+ * pipck_rx_verify_device, pipck_rx_verify_ring{,_n} (a capturing stream takes
+ * the slot groups and keeps no per-ring state), pipck_tx_fill_device,
+ * pipck_tx_fill_ring and pipck_fwd_rewrite_ring.  Calls from several host
+ * threads on streams of their own are independent.
+ * NOT capturable: pipck_gen_ragged_layout and pipck_gen_zipf_lengths (they
+ * allocate and synchronise), and the whole host ABI (pipck_ctx_*,
+ * pipck_host_*, pipck_txq_*, pipck_rxq_*, pipck_rx_verify), which owns its
+ * streams and waits for them. */
 /* d_pseudo == NULL selects pip_ip_checksum semantics (no pseudo-header,
  * pip_checksum.cpp:35-39).  Otherwise the result is
  *   ~fold(pseudo[flow] + hi16(len) + lo16(len) + sum16be(bytes))

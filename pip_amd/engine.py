@@ -223,7 +223,9 @@ def checksum_packed(arena, lens, tile_chunk, n: int | None = None, pseudo=None, 
     packet lengths, tile_chunk = packed_index(lens); packet i at 16 * (chunks before i).
     The device bounds every tile by the arena's size (err: optional device int32,
     OR-ed with 1 << PIPCK_ERANGE for a tile past it, whose results are then 0) and
-    every flow_of entry by n_flows (default: the whole pseudo table, as _n_flows)."""
+    every flow_of entry by n_flows (default: the whole pseudo table, as _n_flows).
+    The first call on a new index tensor reads the index's total back once, which synchronises the
+    host (_check_packed); inside a graph capture that read is skipped."""
     torch = _torch()
     n = lens.numel() if n is None else n
     if out is None:
@@ -237,6 +239,9 @@ def checksum_packed(arena, lens, tile_chunk, n: int | None = None, pseudo=None, 
 
 def verify_packed(arena, lens, tile_chunk, n: int | None = None, pseudo=None, n_flows: int | None = None,
                   flow_of=None, flow_origin: int = 0, ok=None, err=None):
+    """RX verification of a packed batch (pipck_verify_packed_n, bounded as checksum_packed).
+    The first call on a new index tensor reads the index's total back once, which synchronises the
+    host (_check_packed); inside a graph capture that read is skipped."""
     torch = _torch()
     n = lens.numel() if n is None else n
     if ok is None:
@@ -270,7 +275,14 @@ def _check_packed(arena, lens, tile_chunk, n, unit: int = 16):
     against the arena on every call.  An index refilled through a raw pointer
     (a custom kernel writing into a reused tile_off) does not bump _version, so
     this guard can keep its old total; the device bound (the _n calls) still
-    refuses every tile past the arena (PIPCK_ERANGE, results 0)."""
+    refuses every tile past the arena (PIPCK_ERANGE, results 0).
+
+    The read of a new index's total synchronises the host with the index's
+    stream: once per index tensor and version, never again on a cached one.
+    While the current stream is being captured into a graph that read is not
+    allowed, so for an index without a cached total it is skipped (and nothing
+    is cached): the device bound of the _n calls is then the only guard, and it
+    still refuses every tile past the arena."""
     import weakref
 
     if n > lens.numel() or tile_chunk.numel() < (n + 63) // 64 + 1:
@@ -278,6 +290,8 @@ def _check_packed(arena, lens, tile_chunk, n, unit: int = 16):
     ent = _packed_total.get(id(tile_chunk))
     if ent is not None and ent[0]() is tile_chunk and ent[1] == tile_chunk._version and ent[2] == n:
         chunks = ent[3]
+    elif tile_chunk.is_cuda and _torch().cuda.is_current_stream_capturing():
+        return
     else:
         chunks = int(tile_chunk[(n + 63) // 64].item())
         if len(_packed_total) > 64:
@@ -292,7 +306,9 @@ def checksum_packed_bytes(arena, lens, tile_off, n: int | None = None, pseudo=No
                           flow_of=None, flow_origin: int = 0, out=None, err=None):
     """Byte-packed ragged batch (pipck_checksum_packed_bytes_n): packets back to back with no padding,
     lens = device int16/uint16 lengths, tile_off = packed_bytes_index(lens); arena 128-byte aligned.
-    Tiles are bounded by the arena's size on the device (err as checksum_packed)."""
+    Tiles are bounded by the arena's size on the device (err as checksum_packed).
+    The first call on a new index tensor reads the index's total back once, which synchronises the
+    host (_check_packed); inside a graph capture that read is skipped."""
     torch = _torch()
     n = lens.numel() if n is None else n
     if out is None:
@@ -307,7 +323,8 @@ def checksum_packed_bytes(arena, lens, tile_off, n: int | None = None, pseudo=No
 def prepare_checksum_packed_bytes(arena, lens, tile_off, n: int | None = None, pseudo=None,
                                   n_flows: int | None = None, flow_of=None, flow_origin: int = 0, out=None, err=None):
     """checksum_packed_bytes with its arguments checked and bound once (as
-    prepare_checksum_fixed); returns (run, out)."""
+    prepare_checksum_fixed); returns (run, out).  Preparing reads a new index's total back once
+    (a host synchronisation, _check_packed); run() never does."""
     torch = _torch()
     n = lens.numel() if n is None else n
     if out is None:
@@ -320,6 +337,10 @@ def prepare_checksum_packed_bytes(arena, lens, tile_off, n: int | None = None, p
 
 def verify_packed_bytes(arena, lens, tile_off, n: int | None = None, pseudo=None, n_flows: int | None = None,
                         flow_of=None, flow_origin: int = 0, ok=None, err=None):
+    """RX verification of a byte-packed batch (pipck_verify_packed_bytes_n, bounded as
+    checksum_packed_bytes).
+    The first call on a new index tensor reads the index's total back once, which synchronises the
+    host (_check_packed); inside a graph capture that read is skipped."""
     torch = _torch()
     n = lens.numel() if n is None else n
     if ok is None:
@@ -349,7 +370,9 @@ def rx_verify_ring(ring, stride: int, lens, n: int | None = None, ok=None, err=N
 def rx_verify_device(arena, lens, tile_off, n: int | None = None, ok=None, err=None):
     """Received IP packets in device memory, byte-packed (pipck_rx_verify_device): the
     PIPCK_RX_* bits per packet (uint8), as pipck_rx_verify gives for the same bytes in
-    host memory.  Tiles are bounded by the arena's size on the device (err as checksum_packed)."""
+    host memory.  Tiles are bounded by the arena's size on the device (err as checksum_packed).
+    The first call on a new index tensor reads the index's total back once, which synchronises the
+    host (_check_packed); inside a graph capture that read is skipped."""
     torch = _torch()
     n = lens.numel() if n is None else n
     if ok is None:
@@ -369,7 +392,9 @@ def tx_fill_device(arena, lens, tile_off, n: int | None = None, flags: int = 0, 
     header checksum and the TCP / UDP / ICMP / ICMPv6 checksum of every frame are computed and
     stored into `arena` in place, as pip's TX path writes them; returns the PIPCK_TX_* bits per
     frame (uint8).  flags: TX_UDP_ZERO_AS_ONES.  Tiles are bounded by the arena's size on the
-    device: one reaching past it is neither read nor written (err as checksum_packed)."""
+    device: one reaching past it is neither read nor written (err as checksum_packed).
+    The first call on a new index tensor reads the index's total back once, which synchronises the
+    host (_check_packed); inside a graph capture that read is skipped."""
     torch = _torch()
     n = lens.numel() if n is None else n
     if done is None:

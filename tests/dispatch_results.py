@@ -136,18 +136,33 @@ def oracle_checksums(host, offs, lens, ps) -> np.ndarray:
 # ----------------------------------------------------------------------------
 # packets at given places: the fixed, ragged and packed groups
 # ----------------------------------------------------------------------------
-def packets_batch(size: int, offs, lens, flow_idx, key, planted: int = 0) -> SimpleNamespace:
+def variant_key(tag: int, key, variant: int) -> list:
+    """The rng key of a builder: [tag, *key], with a non-zero `variant` appended -- other contents
+    on the same layout; variant 0 draws the bytes these builders have always drawn."""
+    return [tag, *key] + ([variant] if variant else [])
+
+
+def damage(host, offs, lens, rng, variant: int = 0) -> None:
+    """verify_sealing.damage with its index classes shifted by 3 * variant: packet i is damaged as
+    class (i + 3 * variant) % 8, so the packets that fail in variant 1 (i % 8 in {5, 7}) are not
+    those of variant 0 (i % 8 in {0, 2}).  Variant 0 is verify_sealing.damage itself."""
+    if variant:
+        offs, lens = np.roll(np.asarray(offs), 3 * variant), np.roll(np.asarray(lens), 3 * variant)
+    vs.damage(host, offs, lens, rng)
+
+
+def packets_batch(size: int, offs, lens, flow_idx, key, planted: int = 0, variant: int = 0) -> SimpleNamespace:
     """`size` random bytes whose packets (offs, lens; flows flow_idx, None: no pseudo-header) are
     sealed and then damaged; `planted` packets, spread over the batch, are zeroed after that.
     Gives host, offs, lens, the field offsets, and the reference's verdicts and checksums of the
-    final bytes."""
-    rng = np.random.default_rng([11, *key])
+    final bytes.  `variant`: second contents on the same layout (variant_key, damage)."""
+    rng = np.random.default_rng(variant_key(11, key, variant))
     host = rng.integers(0, 256, size, dtype=np.uint8)
     offs, lens = np.asarray(offs, dtype=np.int64), np.asarray(lens, dtype=np.int64)
     n = len(lens)
     ps = pseudo_of(flow_idx)
     fields = vs.seal(host, offs, lens, ps, oracle(), rng)
-    vs.damage(host, offs, lens, rng)
+    damage(host, offs, lens, rng, variant)
     for k in range(planted):
         i = n * (2 * k + 1) // (2 * planted)
         host[offs[i]:offs[i] + lens[i]] = 0
@@ -162,14 +177,15 @@ def fixed_shape(group: str):
 
 
 @functools.lru_cache(maxsize=None)
-def fixed_batch(shape, with_pseudo: bool) -> SimpleNamespace:
+def fixed_batch(shape, with_pseudo: bool, variant: int = 0) -> SimpleNamespace:
     """The batch of one fixed shape, shared by its checksum and its verify group: exactly
     n * stride bytes, the stride padding random.  `origin`: the flow origin of the call."""
     stride, length, n, off = shape
     origin = NF * ((1 << 30) + 5 * stride + length) - 3 if with_pseudo else 0  # packets 3 and 4 on flows 0 and 1
     b = packets_batch(n * stride, np.arange(n, dtype=np.int64) * stride, np.full(n, length),
                       implicit_flows(origin, n) if with_pseudo else None,
-                      (1, stride, length, n, off, int(with_pseudo)), planted=0 if with_pseudo else PLANTED)
+                      (1, stride, length, n, off, int(with_pseudo)), planted=0 if with_pseudo else PLANTED,
+                      variant=variant)
     b.origin = origin
     return b
 
@@ -213,12 +229,12 @@ def chain_begin(n_segs: int) -> np.ndarray:
     return np.array(list(range(0, n_segs, 3)) + [n_segs], dtype=np.int64)
 
 
-def chains_batch(size: int, offs, lens, key) -> SimpleNamespace:
+def chains_batch(size: int, offs, lens, key, variant: int = 0) -> SimpleNamespace:
     """`size` random bytes under the descriptors (offs, lens), grouped by chain_begin, every chain
     on flow 0.  A 16-bit field at offset 16 of every chain's first segment is given the value that
     brings the chain's checksum to 0x0000 (the oracle's chain checksum with the field zeroed), then
     the first segments are damaged.  `checksums`: saturation_cases.chain_checksum of the final bytes."""
-    rng = np.random.default_rng([12, *key])
+    rng = np.random.default_rng(variant_key(12, key, variant))
     host = rng.integers(0, 256, size, dtype=np.uint8)
     offs, lens = np.asarray(offs, dtype=np.int64), np.asarray(lens, dtype=np.int64)
     begin = chain_begin(len(lens))
@@ -230,7 +246,7 @@ def chains_batch(size: int, offs, lens, key) -> SimpleNamespace:
         c = oracle().inet_checksum_chain([host[int(o):int(o) + int(n)].tobytes() for o, n in zip(offs[a:b], lens[a:b])],
                                          flow0[3], flow0[1], flow0[2])
         host[at], host[at + 1] = c >> 8, c & 0xFF
-    vs.damage(host, offs[begin[:-1]], lens[begin[:-1]], rng)
+    damage(host, offs[begin[:-1]], lens[begin[:-1]], rng, variant)
     want = np.array([sc.chain_checksum(host, offs[a:b], lens[a:b], flow0) for a, b in zip(begin[:-1], begin[1:])],
                     dtype=np.uint16)
     return SimpleNamespace(host=host, offs=offs, lens=lens, begin=begin, n=len(begin) - 1, checksums=want,
@@ -278,17 +294,17 @@ def twin_frames(n: int, seed: int, checksummed: bool = True, l4_len: int = 0, st
     return host, starts, lens
 
 
-def frames_batch(host, starts, lens, key, tx: bool = False) -> SimpleNamespace:
+def frames_batch(host, starts, lens, key, tx: bool = False, variant: int = 0) -> SimpleNamespace:
     """The frames host[start:start + len] with verify_sealing.damage applied over every frame's L4
     range (a flipped bit in one frame of eight, a sum-neutral swap in another, two bytes exchanged
     in a third).  RX: `verdicts`, rx_reference.verdict per frame.  TX: `filled`, the whole image
     with every frame replaced by tx_reference.fill's, and `done`, its PIPCK_TX_* bits.  `host` is
     copied, not modified."""
-    rng = np.random.default_rng([14, *key])
+    rng = np.random.default_rng(variant_key(14, key, variant))
     host = np.array(host, dtype=np.uint8, copy=True)
     starts, lens = np.asarray(starts, dtype=np.int64), np.asarray(lens, dtype=np.int64)
     ranges = [R.l4_range(host[int(s):int(s) + int(n)].tobytes()) for s, n in zip(starts, lens)]
-    vs.damage(host, [int(s) + a for s, (a, _) in zip(starts, ranges)], [z - a for a, z in ranges], rng)
+    damage(host, [int(s) + a for s, (a, _) in zip(starts, ranges)], [z - a for a, z in ranges], rng, variant)
     b = SimpleNamespace(host=host, starts=starts, lens=lens, n=len(lens))
     frames = [host[int(s):int(s) + int(n)].tobytes() for s, n in zip(starts, lens)]
     if not tx:
