@@ -55,9 +55,9 @@ const char* pipck_last_error(void);
  * of the ragged, chain and ring calls.  1.3: the bounded _n forms of the
  * fixed-stride calls (pipck_checksum_fixed_n, pipck_verify_fixed_n,
  * pipck_update_fixed_n).  1.4: pipck_tx_fill_device.  1.5: pipck_tx_fill_ring.
- * 1.6: pipck_fwd_rewrite_ring. */
+ * 1.6: pipck_fwd_rewrite_ring.  1.7: pipck_fwd_rewrite_device. */
 #define PIPCK_VERSION_MAJOR 1
-#define PIPCK_VERSION_MINOR 6
+#define PIPCK_VERSION_MINOR 7
 uint32_t pipck_version(void);
 
 /* ---- flows / pseudo-headers ------------------------------------------ */
@@ -98,8 +98,8 @@ int pipck_flows6_prepare(const pipck_flow6* d_flows, uint32_t n_flows, uint32_t*
  * pipck_packed_index, pipck_packed_bytes_index, pipck_update_fixed{,_n},
  * pipck_rx_verify_device, pipck_rx_verify_ring{,_n} (a capturing stream takes
  * the slot groups and keeps no per-ring state), pipck_tx_fill_device,
- * pipck_tx_fill_ring and pipck_fwd_rewrite_ring.  Calls from several host
- * threads on streams of their own are independent.
+ * pipck_tx_fill_ring, pipck_fwd_rewrite_ring and pipck_fwd_rewrite_device.
+ * Calls from several host threads on streams of their own are independent.
  * NOT capturable: pipck_gen_ragged_layout and pipck_gen_zipf_lengths (they
  * allocate and synchronise), and the whole host ABI (pipck_ctx_*,
  * pipck_host_*, pipck_txq_*, pipck_rxq_*, pipck_rx_verify), which owns its
@@ -755,6 +755,49 @@ typedef struct pipck_fwd_rule {   /* 48 bytes, 16-byte aligned table */
 int pipck_fwd_rewrite_ring(void* d_arena, uint64_t slot_stride, const uint16_t* d_lens, uint64_t n_slots,
                            const pipck_fwd_rule* d_rules, uint32_t n_rules, const uint32_t* d_rule_of,
                            uint32_t flags, uint8_t* d_done, uint32_t* d_err, void* stream);
+
+/* The same rewrite for a byte-packed batch in DEVICE memory -- what
+ * pipck_rx_verify_device has just verified and pipck_host_rx_verify_packed
+ * uploads: capture buffers and socket rings read in order.  Layout, alignment
+ * and index are exactly those of pipck_rx_verify_device and
+ * pipck_tx_fill_device: frame i of d_lens[i] bytes (0..65,535) at d_arena + b_i,
+ * d_tile_off from pipck_packed_bytes_index, the arena 128-byte aligned, readable
+ * and writable to the 16-byte boundary after the last frame.  The rule table,
+ * d_rule_of, flags, the d_done values and PIPCK_FWD_NO_RULE are exactly those of
+ * pipck_fwd_rewrite_ring.  Decisions, in this order:
+ *   - First the tile bound of pipck_tx_fill_device: a tile of 64 frames whose
+ *     bytes, as d_tile_off and d_lens place them, reach past arena_bytes is
+ *     neither read nor written, its frames get d_done 0 and d_err (optional,
+ *     device u32) gets (1 << PIPCK_ERANGE).  Its rules are not consulted: an
+ *     invalid rule there sets no PIPCK_EINVAL bit.
+ *   - Then, per frame, steps 1 to 6 of pipck_fwd_rewrite_ring's list above,
+ *     which stays the one definition; only the refusal d_lens[i] > slot_stride
+ *     drops out, there being no stride.
+ * Reads: per frame only the aligned 16-byte chunks that hold its first
+ * min(length, 96) bytes, never a chunk past the one holding its last byte, and,
+ * only where an IPv6 extension chain carries the L4 fields past them, those
+ * headers, from the frame's own bytes.  Payload and link padding are never read.
+ * Stores: every store instruction covers only bytes of its own frame -- the
+ * named fields, the byte beside the TTL or hop limit (bytes 8-9 of IPv4, 6-7 of
+ * IPv6 are stored together, as the ring call stores them) and the two checksum
+ * fields.  No store spans into another frame and none is a read-modify-write of
+ * a wider unit: a frame that starts at a multiple of 4 gets aligned 32- and
+ * 16-bit stores, one at 2 mod 4 16-bit stores, one at an odd address single
+ * bytes, so the neighbouring frame's bytes in the same dword may be stored by
+ * another lane, wave or block at the same time.  The frames of one call must
+ * not be read or written by other work on the device while it runs.
+ * PIPCK_EINVAL (no launch) for unknown bits in flags (checked first), then for a
+ * null d_arena, d_lens, d_tile_off, d_done or d_rules, n_rules == 0, a rule
+ * table that is not 16-byte aligned or an arena that is not 128-byte aligned;
+ * n_packets == 0 returns PIPCK_OK.  One kernel on `stream`, asynchronous, with
+ * no host-side allocation and no per-call state (capturable in a graph).
+ * Cost on one MI355X: 59-93 ps a frame where frames
+ * start 4-aligned, on 8,920-8,940-byte frames 0.07 of pipck_rx_verify_device's
+ * time; 141-162 ps where they start at every residue and go out byte by byte. */
+int pipck_fwd_rewrite_device(void* d_arena, uint64_t arena_bytes, const uint16_t* d_lens,
+                             const uint64_t* d_tile_off, uint64_t n_packets, const pipck_fwd_rule* d_rules,
+                             uint32_t n_rules, const uint32_t* d_rule_of, uint32_t flags, uint8_t* d_done,
+                             uint32_t* d_err, void* stream);
 
 #ifdef __cplusplus
 }

@@ -115,6 +115,7 @@ SIGNATURES = {
     "pipck_tx_fill_device": (_i32, [_p, _u64, _p, _p, _u64, _u32, _p, _p, _p]),
     "pipck_tx_fill_ring": (_i32, [_p, _u64, _p, _u64, _u32, _p, _p, _p]),
     "pipck_fwd_rewrite_ring": (_i32, [_p, _u64, _p, _u64, _p, _u32, _p, _u32, _p, _p, _p]),
+    "pipck_fwd_rewrite_device": (_i32, [_p, _u64, _p, _p, _u64, _p, _u32, _p, _u32, _p, _p, _p]),
     "pipck_host_rx_verify_packed": (_i32, [_p, _p, _p, _u64, _p, C.POINTER(_u64)]),
     "pipck_rx_verify_ring": (_i32, [_p, _u64, _p, _u64, _p, _p]),
     "pipck_rx_verify_ring_n": (_i32, [_p, _u64, _p, _u64, _p, _p, _p]),

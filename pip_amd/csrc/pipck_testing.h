@@ -130,7 +130,9 @@ extern "C" {
  *   k_ring        (pipck_rx_verify_ring) loads 8 / 12 / 16 / 24 = its loads in flight, 17 /
  *                 25 = 16 / 24 in the interleaved row stream only (default 8, interleaved
  *                 12); blocks 8 / 16 / 32 makes its interleaved row stream cover so many
- *                 slots at a time; its other switches are pipck_tune_ring's, below */
+ *                 slots at a time; its other switches are pipck_tune_ring's, below
+ *   k_fwd_device  (pipck_fwd_rewrite_device) one shape, four tiles of 64 frames per block of
+ *                 four independent waves: it reads no tune word */
 void pipck_tune(uint32_t lanes_per_packet, uint32_t loads_per_lane, uint32_t blocks, uint32_t flags);
 
 /* MEASUREMENT-ONLY probes that CHANGE RESULTS, kept apart from pipck_tune's

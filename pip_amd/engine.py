@@ -480,6 +480,32 @@ def fwd_rewrite_ring(ring, stride: int, lens, rules, rule_of=None, n: int | None
     return done
 
 
+def fwd_rewrite_device(arena, lens, tile_off, rules, rule_of=None, n: int | None = None, flags: int = 0, done=None,
+                       err=None):
+    """NAT and TTL rewrite of the frames of a byte-packed batch in device memory, from their
+    headers alone (pipck_fwd_rewrite_device): the layout of rx_verify_device and tx_fill_device
+    (lens, tile_off = packed_bytes_index(lens), arena 128-byte aligned), the rules, rule_of, flags
+    and done bytes of fwd_rewrite_ring.  A tile reaching past the arena is neither read nor
+    written and a rule index past the table is refused on the device (done 0, nothing stored,
+    1 << PIPCK_ERANGE OR-ed into err, an optional device int32); an invalid rule sets
+    1 << PIPCK_EINVAL there.
+    The first call on a new index tensor reads the index's total back once, which synchronises the
+    host (_check_packed); inside a graph capture that read is skipped."""
+    torch = _torch()
+    n = lens.numel() if n is None else n
+    if rules.dtype != torch.uint8 or rules.dim() != 2 or rules.shape[1] != FWD_RULE_BYTES or rules.shape[0] == 0 or \
+            not rules.is_contiguous() or rules.device != arena.device:
+        raise ValueError("rules must be make_fwd_rules' uint8[n, 48] tensor on the arena's device")
+    if rule_of is not None and (rule_of.element_size() != 4 or n > rule_of.numel()):
+        raise ValueError("rule_of must hold one 32-bit index per frame")
+    if done is None:
+        done = torch.empty(n, dtype=torch.uint8, device=arena.device)
+    _check_packed(arena, lens, tile_off, n, unit=1)
+    call("pipck_fwd_rewrite_device", _ptr(arena), _nbytes(arena), _ptr(lens), _ptr(tile_off), n, _ptr(rules),
+         rules.shape[0], _ptr(rule_of), flags, _ptr(done), _ptr(err), current_stream(arena.device))
+    return done
+
+
 def packed_bytes_index(lens, n: int | None = None):
     """tile_off for a byte-packed batch: the byte offset of every 64th packet (u64 as int64) + the total."""
     torch = _torch()

@@ -45,6 +45,23 @@ TTL / hop limit 255 and its checksums filled again, and every leg starts from a
 copy of that ring: a rewrite decrements every TTL, and none may expire within a
 leg.  After a leg of rewrites pipck_rx_verify_ring_n must give every frame the
 verdict it had (checked).  One JSON line per ring.
+
+    python tools/rx_device_bench.py --fwd-device
+
+times pipck_fwd_rewrite_device (k_fwd_device; the same two rules and flag) on
+byte-packed arenas (--fwd-mixes: an L4 length for every frame, 0 = the Zipf mix;
+with 20- and 40-byte IP headers 64, 1500 and 8900 give frames whose lengths are
+all multiples of 4, so every frame starts 4-aligned and takes dword stores, and
+1499 gives every start residue: halfword and single-byte stores) against
+pipck_rx_verify_device and pipck_tx_fill_device on the same arena and against
+pipck_fwd_rewrite_ring on the same frames in ring slots (each frame's first 96
+bytes copied into a slot: the ring call reads nothing else of a frame).  The legs
+RX, rewrite, TX, ring rewrite, RX rotate over eight rounds of 20 launches after
+40 warm-up launches each, every leg from a copy of the same arena and ring, every
+frame with TTL / hop limit 255 and DONE under all five ops.  One rewrite of each
+layout must give the same bytes and done values, and after a leg of rewrites
+pipck_rx_verify_device must give every frame the verdict it had (both checked).
+One JSON line per arena, with each leg's rounds and their spread.
 """
 from __future__ import annotations
 
@@ -311,6 +328,132 @@ def fwd_rings(a):
         engine.tune()
 
 
+def fwd_device(a):
+    """The --fwd-device legs (see the module docstring)."""
+    import hashlib
+
+    import numpy as np
+    import torch
+
+    from bench import last_kernel
+    from pip_amd import _lib, engine
+    from size_scan import timed_b2b
+
+    engine.require_gpu()
+    sha = hashlib.sha256(_lib.LIBPIPCK.read_bytes()).hexdigest()  # the build this process loaded
+    box = engine.pci_bus_id(torch.cuda.current_device())
+    all_ops = (engine.FWD_SET_SRC | engine.FWD_SET_DST | engine.FWD_SET_SPORT | engine.FWD_SET_DPORT |
+               engine.FWD_DEC_TTL)
+    rules = engine.make_fwd_rules([
+        dict(ops=all_ops, family=4, src=bytes([203, 0, 113, 7]), dst=bytes([198, 51, 100, 9]), sport=40001, dport=53),
+        dict(ops=all_ops, family=6, src=bytes.fromhex("20010db885a3000000008a2e03707334"),
+             dst=bytes.fromhex("20010db8000000000000ff0000428329"), sport=40001, dport=53)])
+    flags = engine.FWD_UDP_ZERO_AS_ONES
+    for l4 in [int(x) for x in a.fwd_mixes.split(",")]:
+        n = a.packets if l4 == 0 else min(a.packets, (8 << 30) // (l4 + 30))  # at most ~8 GiB of frames
+        arena, lens, tile_off, kind, start, _ = engine.gen_rx_frames(n, 11, l4_len=l4)
+        total, nbytes = int(tile_off[-1].item()), arena.numel()
+        v6 = kind == 3
+        rule_of = v6.to(torch.int32)
+        # TTL / hop limit 255 (a leg's launches never reach 1), the checksums filled again
+        arena[start[~v6] + 8] = 255
+        arena[start[v6] + 7] = 255
+        engine.tx_fill_device(arena, lens, tile_off)
+        before = arena.clone()
+        flen = lens.to(torch.int64) & 0xFFFF
+        # the same frames in ring slots, for pipck_fwd_rewrite_ring: each frame's first 96 bytes -- the
+        # call reads nothing else of a frame, so the rest of a slot stays unwritten
+        stride = max(1024, (int(flen.max().item()) + 15) // 16 * 16)
+        ring = torch.empty(n * stride, dtype=torch.uint8, device="cuda")
+        rows = ring.view(n, stride)
+        col = torch.arange(96, device="cuda")
+        for lo in range(0, n, 1 << 20):
+            hi = min(n, lo + (1 << 20))
+            idx = (start[lo:hi, None] + col).clamp(max=nbytes - 1)
+            rows[lo:hi, :96] = arena[idx]
+        ring_before = ring.clone()
+        ok = torch.empty(n, dtype=torch.uint8, device="cuda")
+        done = torch.empty(n, dtype=torch.uint8, device="cuda")
+        fdone = torch.empty(n, dtype=torch.uint8, device="cuda")
+        rdone = torch.empty(n, dtype=torch.uint8, device="cuda")
+        assert a.warm + a.iters < 250
+
+        def rx():
+            engine.call("pipck_rx_verify_device", engine._ptr(arena), nbytes, engine._ptr(lens), engine._ptr(tile_off),
+                        n, engine._ptr(ok), None, engine.current_stream())
+
+        def tx():
+            engine.call("pipck_tx_fill_device", engine._ptr(arena), nbytes, engine._ptr(lens), engine._ptr(tile_off),
+                        n, 0, engine._ptr(done), None, engine.current_stream())
+
+        def fwd():
+            engine.call("pipck_fwd_rewrite_device", engine._ptr(arena), nbytes, engine._ptr(lens),
+                        engine._ptr(tile_off), n, engine._ptr(rules), 2, engine._ptr(rule_of), flags,
+                        engine._ptr(fdone), None, engine.current_stream())
+
+        def fring():
+            engine.call("pipck_fwd_rewrite_ring", engine._ptr(ring), stride, engine._ptr(lens), n, engine._ptr(rules),
+                        2, engine._ptr(rule_of), flags, engine._ptr(rdone), None, engine.current_stream())
+
+        rx()
+        verdicts_before = ok.clone()
+        legs = [("rx_a", rx), ("fwd", fwd), ("tx", tx), ("ring", fring), ("rx_b", rx)]
+        ms = {k: [] for k, _ in legs}
+        kern = {}
+        for rnd in range(a.rounds):
+            for name, fn in legs[rnd % 5:] + legs[:rnd % 5]:
+                arena.copy_(before)  # every leg on the same bytes: a rewrite decrements every TTL
+                ring.copy_(ring_before)
+                for _ in range(a.warm):
+                    fn()
+                ms[name].append(timed_b2b(fn, a.iters))
+                kern[name] = last_kernel().split("(")[0]
+        # one rewrite of each layout from the same bytes gives the same first 96 bytes and done values
+        arena.copy_(before)
+        ring.copy_(ring_before)
+        fwd()
+        fring()
+        same = bool(torch.equal(fdone, rdone))
+        for lo in range(0, n, 1 << 20):
+            hi = min(n, lo + (1 << 20))
+            idx = (start[lo:hi, None] + col).clamp(max=nbytes - 1)
+            same = same and bool(torch.equal(torch.where(col < flen[lo:hi, None], arena[idx], 0),
+                                             torch.where(col < flen[lo:hi, None], rows[lo:hi, :96], 0)))
+        # the sums are preserved: after a leg of rewrites every frame has the verdict it had
+        for _ in range(a.warm + a.iters - 1):
+            fwd()
+        rx()
+        kept = bool(torch.equal(ok, verdicts_before))
+        med = {k: statistics.median(v) for k, v in ms.items()}
+        spread = {k: (max(v) - min(v)) / med[k] for k, v in ms.items()}
+        rx_mean = (med["rx_a"] + med["rx_b"]) / 2
+        hist = lambda t: {int(k): int(c) for k, c in zip(*np.unique(t.cpu().numpy(), return_counts=True))}  # noqa: E731
+        residues = torch.bincount(start % 4, minlength=4).tolist()
+        print(json.dumps({"what": "fwd_rewrite_device_vs_rx_verify_device_vs_tx_fill_device_vs_fwd_rewrite_ring",
+                          "l4_len": l4 or "zipf", "frames": n, "frame_bytes": total, "ring_stride": stride,
+                          "starts_mod_4": residues,
+                          "rx_kernel": kern["rx_a"], "tx_kernel": kern["tx"], "fwd_kernel": kern["fwd"],
+                          "ring_kernel": kern["ring"],
+                          **{k + "_ms": round(v, 4) for k, v in med.items()},
+                          **{k + "_rounds_ms": [round(x, 4) for x in v] for k, v in ms.items()},
+                          **{k + "_spread": round(v, 4) for k, v in spread.items()},
+                          "fwd_over_rx": round(med["fwd"] / rx_mean, 4),
+                          "fwd_over_tx": round(med["fwd"] / med["tx"], 4),
+                          "fwd_over_ring": round(med["fwd"] / med["ring"], 4),
+                          "rx_minus_fwd_ms": round(rx_mean - med["fwd"], 4),
+                          "larger_round_spread_ms": round(max(max(ms["fwd"]) - min(ms["fwd"]),
+                                                              max(ms["rx_a"] + ms["rx_b"]) - min(ms["rx_a"] + ms["rx_b"])), 4),
+                          "fwd_ps_per_frame": round(med["fwd"] * 1e9 / n, 1),
+                          "ring_ps_per_frame": round(med["ring"] * 1e9 / n, 1),
+                          "warm": a.warm, "rounds": a.rounds, "iters": a.iters,
+                          "verdicts_kept_by_fwd": kept, "same_as_ring": same, "fwd_done": hist(fdone),
+                          "verdicts": hist(verdicts_before), "pci_bus_id": box, "lib_sha256": sha}), flush=True)
+        assert kept, "pipck_fwd_rewrite_device changed an RX verdict"
+        assert same, "pipck_fwd_rewrite_device and pipck_fwd_rewrite_ring differ on the same frames"
+        del arena, before, ring, rows, ring_before, lens, tile_off, ok, done, fdone, rdone, rule_of, verdicts_before
+        torch.cuda.empty_cache()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--packets", type=int, default=8 << 20)
@@ -329,7 +472,15 @@ def main():
                     help="pipck_tx_fill_ring against k_ring on the --rings; nothing else runs")
     ap.add_argument("--fwd-rings", action="store_true",
                     help="pipck_fwd_rewrite_ring against pipck_tx_fill_ring and k_ring on the --rings; nothing else runs")
+    ap.add_argument("--fwd-device", action="store_true",
+                    help="pipck_fwd_rewrite_device against pipck_rx_verify_device, pipck_tx_fill_device and "
+                         "pipck_fwd_rewrite_ring on the --fwd-mixes; nothing else runs")
+    ap.add_argument("--fwd-mixes", default="64,1500,8900,0,1499",
+                    help="L4 lengths (0 = Zipf) of the --fwd-device arenas")
     a = ap.parse_args()
+    if a.fwd_device:
+        a.iters, a.rounds = a.iters or 20, a.rounds or 8
+        return fwd_device(a)
     if a.fwd_rings:
         a.iters, a.rounds = a.iters or 20, a.rounds or 8
         return fwd_rings(a)
