@@ -55,9 +55,12 @@ const char* pipck_last_error(void);
  * of the ragged, chain and ring calls.  1.3: the bounded _n forms of the
  * fixed-stride calls (pipck_checksum_fixed_n, pipck_verify_fixed_n,
  * pipck_update_fixed_n).  1.4: pipck_tx_fill_device.  1.5: pipck_tx_fill_ring.
- * 1.6: pipck_fwd_rewrite_ring.  1.7: pipck_fwd_rewrite_device. */
+ * 1.6: pipck_fwd_rewrite_ring.  1.7: pipck_fwd_rewrite_device.
+ * 1.8: pipck_fwd_classify_ring, pipck_fwd_classify_device and the host
+ * functions of their binding table (pipck_fwd_key_hash, pipck_fwd_table_build,
+ * pipck_fwd_frame_key). */
 #define PIPCK_VERSION_MAJOR 1
-#define PIPCK_VERSION_MINOR 7
+#define PIPCK_VERSION_MINOR 8
 uint32_t pipck_version(void);
 
 /* ---- flows / pseudo-headers ------------------------------------------ */
@@ -98,7 +101,8 @@ int pipck_flows6_prepare(const pipck_flow6* d_flows, uint32_t n_flows, uint32_t*
  * pipck_packed_index, pipck_packed_bytes_index, pipck_update_fixed{,_n},
  * pipck_rx_verify_device, pipck_rx_verify_ring{,_n} (a capturing stream takes
  * the slot groups and keeps no per-ring state), pipck_tx_fill_device,
- * pipck_tx_fill_ring, pipck_fwd_rewrite_ring and pipck_fwd_rewrite_device.
+ * pipck_tx_fill_ring, pipck_fwd_rewrite_ring, pipck_fwd_rewrite_device,
+ * pipck_fwd_classify_ring and pipck_fwd_classify_device.
  * Calls from several host threads on streams of their own are independent.
  * NOT capturable: pipck_gen_ragged_layout and pipck_gen_zipf_lengths (they
  * allocate and synchronise), and the whole host ABI (pipck_ctx_*,
@@ -798,6 +802,134 @@ int pipck_fwd_rewrite_device(void* d_arena, uint64_t arena_bytes, const uint16_t
                              const uint64_t* d_tile_off, uint64_t n_packets, const pipck_fwd_rule* d_rules,
                              uint32_t n_rules, const uint32_t* d_rule_of, uint32_t flags, uint8_t* d_done,
                              uint32_t* d_err, void* stream);
+
+/* ---- flow classification: d_rule_of from the frames themselves ------------ */
+/* The rewrite calls take one rule index per frame.  pipck_fwd_classify_ring and
+ * pipck_fwd_classify_device produce it on the device: per frame they parse the
+ * headers, look the frame's 5-tuple up in a binding table in DEVICE memory and
+ * write d_rule_of -- so verify -> classify -> rewrite can be enqueued on one
+ * stream, or captured in one graph, with no host work in between.
+ *
+ * Key.  A frame has a key when it is well-formed (step 3 of
+ * pipck_fwd_rewrite_ring's list), its upper layer is located exactly as
+ * pipck_tx_fill_device locates it (not for an IPv4 fragment, an IPv6 fragment
+ * header with an offset or M, a routing header, a ninth extension header or an
+ * extension header that does not fit in the payload), its protocol is TCP, UDP,
+ * ICMP over IPv4 or ICMPv6 over IPv6 and its L4 length is at least 20 (TCP) or 8
+ * (the others): exactly the frames an address-and-port rule of their family
+ * rewrites or finds expired.  The key is then the family, the protocol, the two
+ * addresses as wire bytes (IPv4: the first 4 bytes, the other 12 zero) and, for
+ * TCP and UDP, the four port bytes at message offset 0 (zero for ICMP / ICMPv6).
+ *
+ * Hash, in plain integer arithmetic modulo 2^32, so any binding can build a
+ * table: read the key's 40 bytes as ten little-endian u32 k[0..9]; start with
+ * x = 0; for each k[j] in order  x = rotl32(x ^ k[j], 13) * 0x9E3779B1;  then
+ * x ^= x >> 16;  x *= 0x85EBCA6B;  x ^= x >> 13.  The all-zero key hashes to
+ * 0x00000000; {src 10.0.0.1, dst 10.0.0.2, sport 1234, dport 80, proto 6,
+ * family 4} hashes to 0x1C838748.
+ *
+ * Table.  n_slots entries of 48 bytes, n_slots a power of two up to 2^31,
+ * 16-byte aligned in device memory.  An entry with tag 0 is empty; an occupied
+ * one has tag = pipck_fwd_key_hash(key) | 0x80000000.  Lookup, for
+ * p = 0 .. PIPCK_FWD_MAX_PROBE - 1, looks at entry (hash + p) & (n_slots - 1):
+ * a tag of 0 ends the search as a miss; a tag equal to hash | 0x80000000
+ * together with all 40 key bytes equal is a hit; after 64 probes the search
+ * ends as a miss.  The loop is bounded whatever the table holds and every index
+ * is masked, so a corrupt or foreign table can give wrong rules but never a
+ * read outside n_slots entries and never an unbounded loop.  `rule` is not
+ * bounded here: the rewrite call bounds it against its own n_rules.
+ * Keep the load at or below 0.5: linear probing with this hash, measured on a
+ * CPU over sequential-port IPv4 bindings, random IPv6 bindings and one host's
+ * DNS-style bindings, had a longest probe of 14-26 at 4 K slots, 22-23 at 64 K
+ * and 37-45 at 1 M slots at load 0.5 (8-9 at 64 K slots and load 0.25), but
+ * 120-132 at 64 K slots and load 0.75 -- past the bound of 64. */
+typedef struct pipck_fwd_key {   /* 40 bytes */
+    uint8_t src[16];   /* wire bytes; IPv4 uses the first 4, the other 12 are zero */
+    uint8_t dst[16];
+    uint8_t sport[2];  /* wire bytes; zero for ICMP and ICMPv6 */
+    uint8_t dport[2];
+    uint8_t proto;     /* 6, 17, 1 (IPv4 only), 58 (IPv6 only) */
+    uint8_t family;    /* 4 or 6 */
+    uint8_t pad[2];    /* zero */
+} pipck_fwd_key;
+typedef struct pipck_fwd_entry { /* 48 bytes: three 16-byte chunks, like pipck_fwd_rule */
+    pipck_fwd_key key;
+    uint32_t rule;     /* what d_rule_of receives on a hit; may be PIPCK_FWD_NO_RULE */
+    uint32_t tag;      /* 0 = empty; else pipck_fwd_key_hash(key) | 0x80000000 */
+} pipck_fwd_entry;
+#define PIPCK_FWD_MAX_PROBE    64u
+#define PIPCK_FWD_CLASS_HIT     1u   /* d_class values, exclusive; 0 = malformed or refused */
+#define PIPCK_FWD_CLASS_MISS    2u
+#define PIPCK_FWD_CLASS_UNKEYED 4u
+#define PIPCK_FWD_CLASS_PASSED  8u
+
+/* Host functions: pure CPU, no device, usable without a GPU.
+ * pipck_fwd_key_hash: the hash above (0 for a null key).
+ * pipck_fwd_table_build zeroes table[0, n_slots), then inserts the keys in
+ * order, key i with rules[i], each at the first empty entry of its probe
+ * sequence.  PIPCK_EINVAL for a null table, null keys or rules with n_keys > 0,
+ * n_slots zero, not a power of two or above 2^31, a key with nonzero pad, a
+ * family that is neither 4 nor 6, family 4 with a nonzero address byte 4..15, a
+ * protocol outside {6, 17, 1 with family 4, 58 with family 6}, nonzero ports
+ * with ICMP / ICMPv6, or a duplicate key; PIPCK_ERANGE when a key finds no empty
+ * entry within 64 probes.  On success the table is fully determined by this
+ * rule (byte-comparable with any other implementation of it); on failure its
+ * contents are unspecified.  The caller uploads it to a 16-byte-aligned device
+ * buffer.
+ * pipck_fwd_frame_key returns 1 and writes *key when the frame of len bytes has
+ * a key by the rules above, and 0 when it has none or an argument is null; it
+ * reads nothing past len.  This is how a host turns a frame reported as
+ * PIPCK_FWD_CLASS_MISS into a new binding. */
+uint32_t pipck_fwd_key_hash(const pipck_fwd_key* key);
+int pipck_fwd_table_build(const pipck_fwd_key* keys, const uint32_t* rules, uint64_t n_keys, pipck_fwd_entry* table,
+                          uint64_t n_slots);
+int pipck_fwd_frame_key(const void* frame, uint32_t len, pipck_fwd_key* key);
+
+/* The device calls.  Layouts and host-side argument rules are those of
+ * pipck_fwd_rewrite_ring and pipck_fwd_rewrite_device respectively; the arena
+ * is const: NO byte of it is ever written.  d_rule_of[i] (u32, required)
+ * receives the frame's rule index, d_class[i] (u8, optional) one of the
+ * PIPCK_FWD_CLASS_* values or 0.  d_ok (optional) holds the PIPCK_RX_* verdicts
+ * of the same frames.  Per frame, the first rule that applies decides:
+ *   1. Layout refusal -- ring: d_lens[i] > slot_stride; byte-packed: the tile
+ *      bound of pipck_tx_fill_device, for all frames of the tile.  The frame is
+ *      not read, d_rule_of[i] = PIPCK_FWD_NO_RULE, class 0, d_err (optional,
+ *      device u32) gets (1 << PIPCK_ERANGE).
+ *   2. Verdict gate, when d_ok is given and (d_ok[i] & ok_mask) != ok_mask: the
+ *      frame is not read, PIPCK_FWD_NO_RULE, class PIPCK_FWD_CLASS_PASSED, no
+ *      error bit.  ok_mask = 3 lets verified and unchecked frames through,
+ *      ok_mask = 7 only verified ones, ok_mask = 0 every frame.
+ *   3. A malformed frame (step 3 of pipck_fwd_rewrite_ring's list):
+ *      PIPCK_FWD_NO_RULE, class 0, no error bit.
+ *   4. A well-formed frame without a key (above): other_rule, class
+ *      PIPCK_FWD_CLASS_UNKEYED.  A router gives these its DEC_TTL-only rule.
+ *   5. A keyed frame is looked up: a hit gives the entry's rule and class
+ *      PIPCK_FWD_CLASS_HIT, a miss miss_rule and class PIPCK_FWD_CLASS_MISS.
+ * miss_rule and other_rule may be any u32, PIPCK_FWD_NO_RULE included.
+ * Reads are exactly those of the rewrite calls: the aligned 16-byte chunks
+ * holding a frame's first min(length, 96) bytes, never a chunk past the one
+ * holding its last byte, and the frame's own bytes only where an IPv6 extension
+ * chain carries the ports past them; a gated or refused frame loads nothing.
+ * Of the table a probe that does not match reads 16 bytes, a hit 48.  d_rule_of
+ * and d_class are never written outside [0, n).
+ * PIPCK_EINVAL (no launch) for an ok_mask above 7 (checked first), then, unless
+ * the frame count is 0 (PIPCK_OK), for a null d_arena, d_lens, d_table,
+ * d_rule_of or (byte-packed) d_tile_off, n_slots zero, not a power of two or
+ * above 2^31, a table that is not 16-byte aligned, and the layout's own
+ * alignment and stride rules.  One kernel on `stream`, asynchronous, with no
+ * allocation and no per-call state (capturable in a graph).
+ * Cost on one MI355X, every frame a hit in a table of
+ * 65,536 slots at load 0.5: 39-59 ps a frame, 0.57-0.72 of the rewrite call's
+ * time on the same frames, about a third of it table probes; on 8,920-8,940-byte
+ * frames 0.035 (ring) and 0.045 (byte-packed) of the RX verifier's time. */
+int pipck_fwd_classify_ring(const void* d_arena, uint64_t slot_stride, const uint16_t* d_lens, uint64_t n_slots_ring,
+                            const pipck_fwd_entry* d_table, uint64_t n_slots, uint32_t miss_rule, uint32_t other_rule,
+                            const uint8_t* d_ok, uint32_t ok_mask, uint32_t* d_rule_of, uint8_t* d_class,
+                            uint32_t* d_err, void* stream);
+int pipck_fwd_classify_device(const void* d_arena, uint64_t arena_bytes, const uint16_t* d_lens,
+                              const uint64_t* d_tile_off, uint64_t n_packets, const pipck_fwd_entry* d_table,
+                              uint64_t n_slots, uint32_t miss_rule, uint32_t other_rule, const uint8_t* d_ok,
+                              uint32_t ok_mask, uint32_t* d_rule_of, uint8_t* d_class, uint32_t* d_err, void* stream);
 
 #ifdef __cplusplus
 }

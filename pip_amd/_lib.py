@@ -53,6 +53,19 @@ FWD_DONE, FWD_EXPIRED, FWD_UNHANDLED = 1, 2, 4  # d_done values
 FWD_NO_RULE = 0xFFFFFFFF  # a d_rule_of entry: pass over the slot
 
 
+class FwdKey(C.Structure):  # pipck_fwd_key: 40 bytes
+    _fields_ = [("src", _u8 * 16), ("dst", _u8 * 16), ("sport", _u8 * 2), ("dport", _u8 * 2), ("proto", _u8),
+                ("family", _u8), ("pad", _u8 * 2)]
+
+
+class FwdEntry(C.Structure):  # pipck_fwd_entry: 48 bytes
+    _fields_ = [("key", FwdKey), ("rule", _u32), ("tag", _u32)]
+
+
+FWD_MAX_PROBE = 64
+FWD_CLASS_HIT, FWD_CLASS_MISS, FWD_CLASS_UNKEYED, FWD_CLASS_PASSED = 1, 2, 4, 8  # d_class values; 0: malformed / refused
+
+
 # name -> (restype, argtypes); must match include/pipck.h (checked by tests/test_abi.py)
 SIGNATURES = {
     "pipck_last_error": (C.c_char_p, []),
@@ -116,6 +129,11 @@ SIGNATURES = {
     "pipck_tx_fill_ring": (_i32, [_p, _u64, _p, _u64, _u32, _p, _p, _p]),
     "pipck_fwd_rewrite_ring": (_i32, [_p, _u64, _p, _u64, _p, _u32, _p, _u32, _p, _p, _p]),
     "pipck_fwd_rewrite_device": (_i32, [_p, _u64, _p, _p, _u64, _p, _u32, _p, _u32, _p, _p, _p]),
+    "pipck_fwd_key_hash": (_u32, [_p]),
+    "pipck_fwd_table_build": (_i32, [_p, _p, _u64, _p, _u64]),
+    "pipck_fwd_frame_key": (_i32, [_p, _u32, _p]),
+    "pipck_fwd_classify_ring": (_i32, [_p, _u64, _p, _u64, _p, _u64, _u32, _u32, _p, _u32, _p, _p, _p, _p]),
+    "pipck_fwd_classify_device": (_i32, [_p, _u64, _p, _p, _u64, _p, _u64, _u32, _u32, _p, _u32, _p, _p, _p, _p]),
     "pipck_host_rx_verify_packed": (_i32, [_p, _p, _p, _u64, _p, C.POINTER(_u64)]),
     "pipck_rx_verify_ring": (_i32, [_p, _u64, _p, _u64, _p, _p]),
     "pipck_rx_verify_ring_n": (_i32, [_p, _u64, _p, _u64, _p, _p, _p]),

@@ -506,6 +506,118 @@ def fwd_rewrite_device(arena, lens, tile_off, rules, rule_of=None, n: int | None
     return done
 
 
+FWD_KEY_BYTES, FWD_ENTRY_BYTES = C.sizeof(_lib.FwdKey), C.sizeof(_lib.FwdEntry)  # 40, 48
+FWD_CLASS_HIT, FWD_CLASS_MISS, FWD_CLASS_UNKEYED, FWD_CLASS_PASSED = (_lib.FWD_CLASS_HIT, _lib.FWD_CLASS_MISS,
+                                                                      _lib.FWD_CLASS_UNKEYED, _lib.FWD_CLASS_PASSED)
+
+
+def fwd_key_bytes(family: int, proto: int, src=b"", dst=b"", sport=0, dport=0) -> bytes:
+    """One pipck_fwd_key as its 40 bytes.  src / dst: the address's wire bytes (4 or 16); sport /
+    dport: a port number, or its 2 wire bytes (0 for ICMP / ICMPv6).  Nothing is validated here:
+    make_fwd_table (pipck_fwd_table_build) refuses an invalid key."""
+    def port(p):
+        return int(p).to_bytes(2, "big") if isinstance(p, int) else bytes(p)
+
+    src, dst, sp, dp = bytes(src), bytes(dst), port(sport), port(dport)
+    if len(src) > 16 or len(dst) > 16 or len(sp) != 2 or len(dp) != 2:
+        raise ValueError("an address has at most 16 bytes and a port 2")
+    out = src.ljust(16, b"\0") + dst.ljust(16, b"\0") + sp + dp + bytes([proto, family, 0, 0])
+    assert len(out) == FWD_KEY_BYTES
+    return out
+
+
+def fwd_frame_key(frame) -> bytes | None:
+    """The 40 key bytes of one frame in host memory (pipck_fwd_frame_key), or None where it has no
+    key: how a frame that fwd_classify_* reported as FWD_CLASS_MISS becomes a new binding."""
+    frame = bytes(frame)
+    key = _lib.FwdKey()
+    buf = C.create_string_buffer(frame, max(len(frame), 1))
+    return bytes(key) if _lib.load().pipck_fwd_frame_key(buf, len(frame), C.byref(key)) else None
+
+
+def build_fwd_table(keys, rules, n_slots: int) -> bytes:
+    """pipck_fwd_table_build on the host: the n_slots * 48 bytes of the binding table that maps
+    keys[i] (fwd_key_bytes' 40 bytes, or a dict / tuple as it takes them) to rules[i].  Raises
+    PipckError: PIPCK_EINVAL for an invalid or duplicate key or a slot count that is no power of
+    two, PIPCK_ERANGE when a key finds no empty entry within 64 probes (keep the load <= 0.5)."""
+    raw = b"".join(fwd_key_bytes(**k) if isinstance(k, dict) else bytes(k) if isinstance(k, (bytes, bytearray))
+                   else fwd_key_bytes(*k) for k in keys)
+    n = len(raw) // FWD_KEY_BYTES
+    if len(raw) != n * FWD_KEY_BYTES or len(rules) != n:
+        raise ValueError("one 40-byte key and one rule index per binding")
+    if n_slots <= 0 or n_slots & (n_slots - 1) or n_slots > 1 << 31:
+        raise ValueError("n_slots must be a power of two from 1 to 2^31")
+    kbuf = (C.c_uint8 * max(len(raw), 1)).from_buffer_copy(raw or b"\0")
+    rbuf = (C.c_uint32 * max(n, 1))(*[int(r) & 0xFFFFFFFF for r in rules])
+    table = (_lib.FwdEntry * n_slots)()
+    call("pipck_fwd_table_build", kbuf, rbuf, n, table, n_slots)
+    return bytes(table)
+
+
+def make_fwd_table(keys, rules, n_slots: int, device=None):
+    """The binding table of fwd_classify_*: build_fwd_table on the host, then uploaded as
+    uint8[n_slots, 48] on `device` (default: the current one).  A fresh allocation, so 16-byte
+    aligned."""
+    torch = _torch()
+    raw = build_fwd_table(keys, rules, n_slots)
+    dev = torch.device("cuda", torch.cuda.current_device()) if device is None else device
+    return torch.frombuffer(bytearray(raw), dtype=torch.uint8).view(-1, FWD_ENTRY_BYTES).to(dev)
+
+
+def _fwd_classify_args(arena, table, n, ok, rule_of, cls):
+    torch = _torch()
+    if table.dtype != torch.uint8 or table.dim() != 2 or table.shape[1] != FWD_ENTRY_BYTES or table.shape[0] == 0 or \
+            not table.is_contiguous() or table.device != arena.device:
+        raise ValueError("table must be make_fwd_table's uint8[n_slots, 48] tensor on the frames' device")
+    if ok is not None and (ok.element_size() != 1 or n > ok.numel()):
+        raise ValueError("ok must hold one verdict byte per frame")
+    if rule_of is None:
+        rule_of = torch.empty(n, dtype=torch.int32, device=arena.device)
+    elif rule_of.element_size() != 4 or n > rule_of.numel():
+        raise ValueError("rule_of must hold one 32-bit index per frame")
+    if cls is not None and (cls.element_size() != 1 or n > cls.numel()):
+        raise ValueError("cls must hold one byte per frame")
+    return rule_of
+
+
+def fwd_classify_ring(ring, stride: int, lens, table, n: int | None = None, miss_rule: int = FWD_NO_RULE,
+                      other_rule: int = FWD_NO_RULE, ok=None, ok_mask: int = 3, rule_of=None, cls=None, err=None):
+    """The rule index of every frame in the fixed-size slots of a device ring, from the frames
+    themselves (pipck_fwd_classify_ring): the frame's 5-tuple is looked up in `table`
+    (make_fwd_table); a hit gives the binding's rule, a miss miss_rule, a well-formed frame
+    without a key other_rule, a malformed one FWD_NO_RULE.  ok: rx_verify_ring's verdict bytes; a
+    frame with (ok & ok_mask) != ok_mask is passed over (FWD_NO_RULE, not read).  The ring is never
+    written.  Returns rule_of (int32), usable directly as fwd_rewrite_ring's rule_of; cls (uint8,
+    optional) receives the FWD_CLASS_* value per frame.  A slot length past the stride is refused
+    on the device (FWD_NO_RULE, class 0, 1 << PIPCK_ERANGE OR-ed into err, an optional device
+    int32)."""
+    n = lens.numel() if n is None else n
+    if n * stride > _nbytes(ring) or n > lens.numel():
+        raise ValueError("ring smaller than n * stride, or fewer lengths than slots")
+    rule_of = _fwd_classify_args(ring, table, n, ok, rule_of, cls)
+    call("pipck_fwd_classify_ring", _ptr(ring), stride, _ptr(lens), n, _ptr(table), table.shape[0],
+         miss_rule & 0xFFFFFFFF, other_rule & 0xFFFFFFFF, _ptr(ok), ok_mask, _ptr(rule_of), _ptr(cls), _ptr(err),
+         current_stream(ring.device))
+    return rule_of
+
+
+def fwd_classify_device(arena, lens, tile_off, table, n: int | None = None, miss_rule: int = FWD_NO_RULE,
+                        other_rule: int = FWD_NO_RULE, ok=None, ok_mask: int = 3, rule_of=None, cls=None, err=None):
+    """The rule index of every frame of a byte-packed batch in device memory
+    (pipck_fwd_classify_device): the layout of rx_verify_device and fwd_rewrite_device, the table,
+    rules, gate and results of fwd_classify_ring.  A tile reaching past the arena is not read: its
+    frames get FWD_NO_RULE, class 0, and 1 << PIPCK_ERANGE is OR-ed into err.
+    The first call on a new index tensor reads the index's total back once, which synchronises the
+    host (_check_packed); inside a graph capture that read is skipped."""
+    n = lens.numel() if n is None else n
+    rule_of = _fwd_classify_args(arena, table, n, ok, rule_of, cls)
+    _check_packed(arena, lens, tile_off, n, unit=1)
+    call("pipck_fwd_classify_device", _ptr(arena), _nbytes(arena), _ptr(lens), _ptr(tile_off), n, _ptr(table),
+         table.shape[0], miss_rule & 0xFFFFFFFF, other_rule & 0xFFFFFFFF, _ptr(ok), ok_mask, _ptr(rule_of), _ptr(cls),
+         _ptr(err), current_stream(arena.device))
+    return rule_of
+
+
 def packed_bytes_index(lens, n: int | None = None):
     """tile_off for a byte-packed batch: the byte offset of every 64th packet (u64 as int64) + the total."""
     torch = _torch()

@@ -62,6 +62,21 @@ frame with TTL / hop limit 255 and DONE under all five ops.  One rewrite of each
 layout must give the same bytes and done values, and after a leg of rewrites
 pipck_rx_verify_device must give every frame the verdict it had (both checked).
 One JSON line per arena, with each leg's rounds and their spread.
+
+    python tools/rx_device_bench.py --fwd-classify
+
+times pipck_fwd_classify_ring / pipck_fwd_classify_device (k_fwd_classify_ring,
+k_fwd_classify_device) on the same --rings and --fwd-mixes against the RX verifier
+and the rewrite of the same layout, the same rotation: the legs RX, classify
+(every frame a hit), classify (the keys removed: every frame a miss at its first
+entry), classify (a table as full of keys no frame has: a miss walks to an empty
+entry), rewrite, RX over eight rounds of 20 launches after 40 warm-up launches
+each.  Every frame first gets the addresses and ports of one of 32,766 bindings
+drawn at random (a third each IPv4 TCP, IPv4 UDP, IPv6 TCP), TTL / hop limit 255
+and its checksums filled again; the table has 65,536 slots (load 0.5).  Before
+anything is timed each table's results are checked on the whole batch (all hits
+with the family's rule / all misses with miss_rule) and the arena compared with
+what it held.  One JSON line per ring and arena.
 """
 from __future__ import annotations
 
@@ -454,6 +469,171 @@ def fwd_device(a):
         torch.cuda.empty_cache()
 
 
+FWD_BINDINGS = 10922  # per class (IPv4 TCP, IPv4 UDP, IPv6 TCP): 32,766 keys, load 0.49997 of 65,536 slots
+FWD_TABLE_SLOTS = 1 << 16
+
+
+def _binding_key(engine, b, dport=53):
+    """Key b of the --fwd-classify table: class b % 3 (IPv4 TCP, IPv4 UDP, IPv6 TCP), the bytes _bind_frames writes."""
+    hi, lo = b >> 8, b & 0xFF
+    if b % 3 < 2:
+        return engine.fwd_key_bytes(4, 17 if b % 3 == 1 else 6, bytes([10, 0, hi, lo]), bytes([198, 51, 100, lo]),
+                                    0x8000 | b, dport)
+    return engine.fwd_key_bytes(6, 6, bytes.fromhex("20010db8") + bytes(10) + bytes([hi, lo]),
+                                bytes.fromhex("20010db8") + bytes(9) + bytes([0xFF, 0, lo]), 0x8000 | b, dport)
+
+
+def _bind_frames(torch, buf, at, kind, seed):
+    """Give every frame (first byte at buf[at[i]]; kind as engine.gen_rx_frames) the addresses and ports of a
+    binding drawn at random from the 3 * FWD_BINDINGS of its class, destination port 53, and TTL / hop limit 255."""
+    g = torch.Generator(device="cuda").manual_seed(seed)
+    v6 = kind == 3
+    b = 3 * torch.randint(0, FWD_BINDINGS, (at.numel(),), device="cuda", generator=g) + \
+        torch.where(v6, 2, torch.where(kind == 2, 1, 0))
+    hi, lo = (b >> 8).to(torch.uint8), (b & 0xFF).to(torch.uint8)
+
+    def put(mask, col, val):
+        idx = at[mask] + col
+        buf[idx] = val[mask] if torch.is_tensor(val) else torch.full_like(idx, val, dtype=torch.uint8)
+
+    v4 = ~v6
+    for col, val in enumerate((10, 0, hi, lo, 198, 51, 100, lo, hi | 0x80, lo, 0, 53), start=12):
+        put(v4, col, val)
+    put(v4, 8, 255)
+    src6 = (0x20, 0x01, 0x0D, 0xB8) + (0,) * 10 + (hi, lo)
+    dst6 = (0x20, 0x01, 0x0D, 0xB8) + (0,) * 9 + (0xFF, 0, lo)
+    for col, val in enumerate(src6 + dst6 + (hi | 0x80, lo, 0, 53), start=8):
+        put(v6, col, val)
+    put(v6, 7, 255)
+
+
+def fwd_classify(a):
+    """The --fwd-classify legs (see the module docstring)."""
+    import hashlib
+
+    import torch
+
+    from bench import last_kernel
+    from pip_amd import _lib, engine
+    from size_scan import timed_b2b
+
+    engine.require_gpu()
+    sha = hashlib.sha256(_lib.LIBPIPCK.read_bytes()).hexdigest()  # the build this process loaded
+    box = engine.pci_bus_id(torch.cuda.current_device())
+    all_ops = (engine.FWD_SET_SRC | engine.FWD_SET_DST | engine.FWD_SET_SPORT | engine.FWD_SET_DPORT |
+               engine.FWD_DEC_TTL)
+    rules = engine.make_fwd_rules([
+        dict(ops=all_ops, family=4, src=bytes([203, 0, 113, 7]), dst=bytes([198, 51, 100, 9]), sport=40001, dport=53),
+        dict(ops=all_ops, family=6, src=bytes.fromhex("20010db885a3000000008a2e03707334"),
+             dst=bytes.fromhex("20010db8000000000000ff0000428329"), sport=40001, dport=53)])
+    flags = engine.FWD_UDP_ZERO_AS_ONES
+    n_keys = 3 * FWD_BINDINGS
+    rule_of_key = [int(b % 3 == 2) for b in range(n_keys)]  # rule 0: IPv4, rule 1: IPv6
+    tables = {"hit": engine.make_fwd_table([_binding_key(engine, b) for b in range(n_keys)], rule_of_key, FWD_TABLE_SLOTS),
+              # the keys removed: every search ends at its first entry
+              "miss": engine.make_fwd_table([], [], FWD_TABLE_SLOTS),
+              # as full as the first, of keys no frame has (destination port 54): a miss walks to an empty entry
+              "miss_full": engine.make_fwd_table([_binding_key(engine, b, 54) for b in range(n_keys)], rule_of_key,
+                                                 FWD_TABLE_SLOTS)}
+    miss_rule = 0x7FFFFFFF
+    configs = [("ring", r) for r in BENCH_RINGS if r[0] in a.rings.split(",")] + \
+              [("packed", int(x)) for x in a.fwd_mixes.split(",") if x]
+    engine.tune(ring_adapt=False)  # RX on rings: k_ring at every fill
+    try:
+        for layout, cfg in configs:
+            if layout == "ring":
+                tag, stride, l4, div = cfg
+                n = a.packets // div
+                arena, lens, kind = engine.gen_rx_ring(n, 11, stride, l4_len=l4)
+                at = torch.arange(n, device="cuda") * stride
+                _bind_frames(torch, arena, at, kind, 12)
+                engine.tx_fill_ring(arena, stride, lens, n)
+                head = (engine._ptr(arena), stride, engine._ptr(lens), n)
+                names = ("pipck_rx_verify_ring_n", "pipck_fwd_classify_ring", "pipck_fwd_rewrite_ring")
+            else:
+                l4 = cfg
+                tag = f"packed_{l4 or 'zipf'}"
+                n = a.packets if l4 == 0 else min(a.packets, (8 << 30) // (l4 + 30))  # at most ~8 GiB of frames
+                arena, lens, tile_off, kind, at, _ = engine.gen_rx_frames(n, 11, l4_len=l4)
+                _bind_frames(torch, arena, at, kind, 12)
+                engine.tx_fill_device(arena, lens, tile_off)
+                head = (engine._ptr(arena), arena.numel(), engine._ptr(lens), engine._ptr(tile_off), n)
+                names = ("pipck_rx_verify_device", "pipck_fwd_classify_device", "pipck_fwd_rewrite_device")
+            fbytes = int((lens.to(torch.int64) & 0xFFFF).sum().item())
+            before = arena.clone()
+            want_rule = (kind == 3).to(torch.int32)
+            ok = torch.empty(n, dtype=torch.uint8, device="cuda")
+            fdone = torch.empty(n, dtype=torch.uint8, device="cuda")
+            rule_of = torch.empty(n, dtype=torch.int32, device="cuda")
+            cls = torch.empty(n, dtype=torch.uint8, device="cuda")
+            assert a.warm + a.iters < 250
+            stream = engine.current_stream()
+
+            def rx():
+                engine.call(names[0], *head, engine._ptr(ok), None, stream)
+
+            def classify(which):
+                def fn():
+                    engine.call(names[1], *head, engine._ptr(tables[which]), FWD_TABLE_SLOTS, miss_rule,
+                                engine.FWD_NO_RULE, engine._ptr(ok), 3, engine._ptr(rule_of), engine._ptr(cls), None,
+                                stream)
+                return fn
+
+            def fwd():
+                engine.call(names[2], *head, engine._ptr(rules), 2, engine._ptr(want_rule), flags, engine._ptr(fdone),
+                            None, stream)
+
+            rx()
+            gated = int(((ok & 3) != 3).sum().item())
+            # what each table gives, before anything is timed: every frame a hit with its family's rule / a miss
+            checks = {}
+            for which in tables:
+                classify(which)()
+                want_cls = engine.FWD_CLASS_HIT if which == "hit" else engine.FWD_CLASS_MISS
+                checks[which] = bool((cls == want_cls).all().item()) and bool(
+                    torch.equal(rule_of, want_rule) if which == "hit" else (rule_of == miss_rule).all().item())
+            assert gated == 0 and all(checks.values()), (tag, gated, checks)
+            assert torch.equal(arena, before), "a classify call wrote the arena"
+            legs = [("rx_a", rx), ("cls_hit", classify("hit")), ("cls_miss", classify("miss")),
+                    ("cls_miss_full", classify("miss_full")), ("fwd", fwd), ("rx_b", rx)]
+            ms = {k: [] for k, _ in legs}
+            kern = {}
+            for rnd in range(a.rounds):
+                k = rnd % len(legs)
+                for name, fn in legs[k:] + legs[:k]:
+                    arena.copy_(before)  # every leg on the same bytes: a rewrite decrements every TTL
+                    for _ in range(a.warm):
+                        fn()
+                    ms[name].append(timed_b2b(fn, a.iters))
+                    kern[name] = last_kernel().split("(")[0]
+            med = {k: statistics.median(v) for k, v in ms.items()}
+            rx_all = ms["rx_a"] + ms["rx_b"]
+            rx_mean = (med["rx_a"] + med["rx_b"]) / 2
+            larger = max(max(ms["cls_hit"]) - min(ms["cls_hit"]), max(rx_all) - min(rx_all))
+            print(json.dumps({"what": "fwd_classify_vs_rx_verify_vs_fwd_rewrite", "layout": layout, "config": tag,
+                              "l4_len": l4 or "zipf", "frames": n, "frame_bytes": fbytes,
+                              "table_slots": FWD_TABLE_SLOTS, "table_keys": n_keys,
+                              "rx_kernel": kern["rx_a"], "cls_kernel": kern["cls_hit"], "fwd_kernel": kern["fwd"],
+                              **{k + "_ms": round(v, 4) for k, v in med.items()},
+                              **{k + "_rounds_ms": [round(x, 4) for x in v] for k, v in ms.items()},
+                              "cls_over_rx": round(med["cls_hit"] / rx_mean, 4),
+                              "cls_over_fwd": round(med["cls_hit"] / med["fwd"], 4),
+                              "rx_minus_cls_ms": round(rx_mean - med["cls_hit"], 4),
+                              "larger_round_spread_ms": round(larger, 4),
+                              "cls_below_rx_by_more_than_the_spread": bool(rx_mean - med["cls_hit"] > larger),
+                              "cls_hit_ps_per_frame": round(med["cls_hit"] * 1e9 / n, 1),
+                              "cls_miss_ps_per_frame": round(med["cls_miss"] * 1e9 / n, 1),
+                              "cls_miss_full_ps_per_frame": round(med["cls_miss_full"] * 1e9 / n, 1),
+                              "fwd_ps_per_frame": round(med["fwd"] * 1e9 / n, 1),
+                              "hit_minus_miss_ps_per_frame": round((med["cls_hit"] - med["cls_miss"]) * 1e9 / n, 1),
+                              "warm": a.warm, "rounds": a.rounds, "iters": a.iters, "checked": checks,
+                              "pci_bus_id": box, "lib_sha256": sha}), flush=True)
+            del arena, before, lens, kind, at, ok, fdone, rule_of, cls, want_rule
+            torch.cuda.empty_cache()
+    finally:
+        engine.tune()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--packets", type=int, default=8 << 20)
@@ -477,7 +657,13 @@ def main():
                          "pipck_fwd_rewrite_ring on the --fwd-mixes; nothing else runs")
     ap.add_argument("--fwd-mixes", default="64,1500,8900,0,1499",
                     help="L4 lengths (0 = Zipf) of the --fwd-device arenas")
+    ap.add_argument("--fwd-classify", action="store_true",
+                    help="pipck_fwd_classify_ring / _device against the RX verifier and the rewrite on the --rings "
+                         "and --fwd-mixes; nothing else runs")
     a = ap.parse_args()
+    if a.fwd_classify:
+        a.iters, a.rounds = a.iters or 20, a.rounds or 8
+        return fwd_classify(a)
     if a.fwd_device:
         a.iters, a.rounds = a.iters or 20, a.rounds or 8
         return fwd_device(a)
